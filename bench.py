@@ -29,6 +29,13 @@ Output: ONE JSON line on rank 0 (the driver contract) with `roofline` for the do
 `cpu_baseline` (the restated CPU reference timed on a bounded sample: the CG path with 1 thread and all host threads where LAPACK is involved, and --
 `cpu_baseline.direct_kkt` -- the reference's DEFAULT direct LDL' KKT solver, the CPU path north_star names), and a compact `summary` as the LAST key
 (the driver keeps the tail of the line: all four rates must survive there).
+
+Plain run vs --full: a plain `python bench.py --gpus N --steps K --warmup W` sets up the headline workload, warms up, times the K steps and prints
+the line (metric, value, unit, ms_per_step, dtype, config); it runs nothing else.  Everything described above that takes work of its own -- the
+roofline timings, cpu_baseline, the other workloads under `extra`, the opt-in variants and Float32 numbers, cfg3's time to solution and, at N > 1,
+the parity leg and the unsharded comparison -- runs only with --full (the --no-* options then leave parts of it out again).
+--dump-outputs DIR: after the timed steps, the arrays the timed path hands its caller (x, y, s as optimize() returns them) as DIR/<name>.npy,
+at most DUMP_LIMIT_BYTES in all; the inputs are seeded, so two builds can be compared output for output.
 """
 import argparse
 import json
@@ -53,6 +60,7 @@ F64_MFMA_PEAK_TF = 78.6    # fp64 matrix peak (the guide lists no fp6
 # profiles/r02_mfma_ceiling_and_gemm_lab.txt); reported beside `peak`, never instead of it
 F64_MFMA_SUSTAINED_TF = 66.9
 METRIC = "ADMM iterations/sec (fp64) at fixed (n,m,nnz,cone)"
+DUMP_LIMIT_BYTES = 60 * 10 ** 6     # --dump-outputs: array bytes in all (the .npy headers stay well inside 64 MB)
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -94,6 +102,40 @@ def psd_useful_flops(d, r=None):
     SYRK d(d+1) r with r = #positive eigenvalues ~ d/2)."""
     r = d / 2.0 if r is None else r
     return (10.0 / 3.0) * d ** 3 + d * (d + 1.0) * r
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# --dump-outputs
+# ---------------------------------------------------------------------------------------------------------------------
+def dump_outputs(dirname, arrays):
+    """Write every array as DIR/<name>.npy (float32 stays float32, everything else float64).  Above DUMP_LIMIT_BYTES in all, every array is cut
+    to the same fraction of its entries, a sorted sample drawn with a fixed seed: the same positions at every run of the same workload."""
+    os.makedirs(dirname, exist_ok=True)
+    arrays = {k: np.ascontiguousarray(a, dtype=np.float32 if a.dtype == np.float32 else np.float64) for k, a in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    for name, a in arrays.items():
+        if total > DUMP_LIMIT_BYTES:
+            keep = a.size * DUMP_LIMIT_BYTES // total
+            a = a[np.sort(np.random.default_rng(0).choice(a.size, size=keep, replace=False))]
+        np.save(os.path.join(dirname, name + ".npy"), a)
+
+
+def caller_arrays(md, w_prev, s, mu):
+    """x, y, s of one problem from its device iterates, as optimize() returns them (reverse_scaling!, src/scaling.jl:170-179; y = -mu)."""
+    x = w_prev[:md.n]
+    if md.settings.scaling != 0:
+        x, s, mu = md.sm.D * x, md.sm.Einv * s, (md.sm.E * mu) * md.sm.cinv
+    return dict(x=x, y=-mu, s=s)
+
+
+def dump_handle_outputs(ctx, args, model):
+    """--dump-outputs of a single-problem workload, read right after the timed steps.  On a sharded handle get_iterates is collective (every
+    rank receives the global vectors), so every rank reads and rank 0 writes."""
+    if not args.dump_outputs:
+        return
+    _, w_prev, s, mu = model.handle.get_iterates()
+    if ctx.rank == 0:
+        dump_outputs(args.dump_outputs, caller_arrays(model, w_prev, s, mu))
 
 
 class Ctx:
@@ -351,6 +393,7 @@ def bench_cfg2(ctx, args, steps, warmup):
     elapsed = ctx.timed(lambda: h.admm_iterate_checked(steps))          # returns after the stream has drained (host sync inside)
     stats1 = h.get_stats()
     assert stats1["admm_iters"] - stats0["admm_iters"] == steps
+    dump_handle_outputs(ctx, args, model)
     kbar = (stats1["kkt_iters_total"] - stats0["kkt_iters_total"]) / max(1, stats1["kkt_solves"] - stats0["kkt_solves"])
     world = ctx.world
     value = whole_job_value(world, steps, elapsed)
@@ -359,31 +402,32 @@ def bench_cfg2(ctx, args, steps, warmup):
     if ctx.rank != 0:
         return out
     ab = algorithmic_bytes(n, m, nnzA, nnzP)
-    # dominant kernel: the fused [P | A'] operator SpMV of the CG iteration (K-bar launches per ADMM iteration).  Duration: HIP events
-    # on the library's stream around R back-to-back launches of exactly that kernel on the live loop state (one event pair per R
-    # launches: the ~5 us of an event pair would swamp a 10-20 us kernel; the launch gap IS included, i.e. the number is conservative).
-    t_op, bytes_op = min(h.time_spmv(cj._ffi.MAT_OP, 200) for _ in range(3))        # best of three event pairs of 200 launches (one read 21.9 us once: r03_bench_all_v2)
-    t_A, bytes_A = min(h.time_spmv(cj._ffi.MAT_A, 200) for _ in range(3))            # all four timed the same way (best of 3 x 200)
-    t_AT, bytes_AT = min(h.time_spmv(cj._ffi.MAT_AT, 200) for _ in range(3))
-    t_P, bytes_P = min(h.time_spmv(cj._ffi.MAT_P, 200) for _ in range(3))
-    achieved = bytes_op / t_op / 1e9
-    traffic, traffic_src = None, None
-    if not args.small:
-        import glob
-        for fpmc in sorted(glob.glob(os.path.join(ROOT, "profiles", "r*_cfg2_pmc_traffic.json"))):
-            try:
-                with open(fpmc) as fh:
-                    traffic = json.load(fh)["kernels"]["k_op_apply"]["hbm_bytes_per_launch"]
-                traffic_src = os.path.relpath(fpmc, ROOT)
-            except Exception:
-                pass
+    if args.full:
+        # dominant kernel: the fused [P | A'] operator SpMV of the CG iteration (K-bar launches per ADMM iteration).  Duration: HIP events
+        # on the library's stream around R back-to-back launches of exactly that kernel on the live loop state (one event pair per R
+        # launches: the ~5 us of an event pair would swamp a 10-20 us kernel; the launch gap IS included, i.e. the number is conservative).
+        t_op, bytes_op = min(h.time_spmv(cj._ffi.MAT_OP, 200) for _ in range(3))        # best of three event pairs of 200 launches (one read 21.9 us once: r03_bench_all_v2)
+        t_A, bytes_A = min(h.time_spmv(cj._ffi.MAT_A, 200) for _ in range(3))            # all four timed the same way (best of 3 x 200)
+        t_AT, bytes_AT = min(h.time_spmv(cj._ffi.MAT_AT, 200) for _ in range(3))
+        t_P, bytes_P = min(h.time_spmv(cj._ffi.MAT_P, 200) for _ in range(3))
+        achieved = bytes_op / t_op / 1e9
+        traffic, traffic_src = None, None
+        if not args.small:
+            import glob
+            for fpmc in sorted(glob.glob(os.path.join(ROOT, "profiles", "r*_cfg2_pmc_traffic.json"))):
+                try:
+                    with open(fpmc) as fh:
+                        traffic = json.load(fh)["kernels"]["k_op_apply"]["hbm_bytes_per_launch"]
+                    traffic_src = os.path.relpath(fpmc, ROOT)
+                except Exception:
+                    pass
 
-    def other(b, t):
-        return dict(achieved=round(b / t / 1e9, 1), frac=round(b / t / 1e9 / HBM_PEAK_GBS, 4), algorithmic_bytes_per_launch=b, avg_launch_us=round(1e6 * t, 3))
-    out["roofline"] = dict(bound="hbm", kernel="k_op_apply (c = [P|A'][v; rho.*(A v)] + sigma v, CSR-stream SpMV)", achieved=round(achieved, 1),
-                           peak=HBM_PEAK_GBS, unit="GB/s", frac=round(achieved / HBM_PEAK_GBS, 4), traffic=traffic, traffic_source=traffic_src,
-                           algorithmic_bytes_per_launch=bytes_op, avg_launch_us=round(t_op * 1e6, 3), launches_timed=200, timing="best of 3 x 200 back-to-back launches",
-                           other={"k_spmv_A_rho (A v)": other(bytes_A, t_A), "k_cg_rhs (A' y)": other(bytes_AT, t_AT), "k_spmv_plain (P x)": other(bytes_P, t_P)})
+        def other(b, t):
+            return dict(achieved=round(b / t / 1e9, 1), frac=round(b / t / 1e9 / HBM_PEAK_GBS, 4), algorithmic_bytes_per_launch=b, avg_launch_us=round(1e6 * t, 3))
+        out["roofline"] = dict(bound="hbm", kernel="k_op_apply (c = [P|A'][v; rho.*(A v)] + sigma v, CSR-stream SpMV)", achieved=round(achieved, 1),
+                               peak=HBM_PEAK_GBS, unit="GB/s", frac=round(achieved / HBM_PEAK_GBS, 4), traffic=traffic, traffic_source=traffic_src,
+                               algorithmic_bytes_per_launch=bytes_op, avg_launch_us=round(t_op * 1e6, 3), launches_timed=200, timing="best of 3 x 200 back-to-back launches",
+                               other={"k_spmv_A_rho (A v)": other(bytes_A, t_A), "k_cg_rhs (A' y)": other(bytes_AT, t_AT), "k_spmv_plain (P x)": other(bytes_P, t_P)})
     b_iter = iteration_bytes(ab, kbar)
     # (`workload` stays under 120 characters: the driver's parsed copy of the line cut the longer string of round 3 in the middle of a word)
     out["config"] = {"workload": "cfg2: random sparse QP n=%d m=%d nnz(A)=%d, Box cone, CG indirect KKT" % (n, m, nnzA),
@@ -423,12 +467,17 @@ def bench_cfg3(ctx, args, steps, warmup):
     _, _, kk0 = B.counters()
     elapsed = ctx.timed(lambda: B.iterate(steps))
     _, _, kk1 = B.counters()
+    if args.dump_outputs:                                    # every problem of the job, in global order (the shards are contiguous)
+        mine = [caller_arrays(md, *B.get_iterates(k)[1:]) for k, md in enumerate(mods)]
+        every = [p for part in ctx.all_gather(mine) for p in part]
+        if ctx.rank == 0:
+            dump_outputs(args.dump_outputs, {key: np.concatenate([p[key] for p in every]) for key in ("x", "y", "s")})
     value = steps / elapsed                                  # one step = one ADMM iteration of ALL problems of the job
     out = dict(value=value, ms_per_step=1e3 * elapsed / steps, steps=steps, warmup=warmup, scaling="strong")
     rank_seconds = ctx.rank_seconds()
     parity = None
     kry_every = ctx.all_gather((kk1 - kk0).astype(np.float64)) if ctx.world > 1 else None
-    if ctx.world > 1 and os.environ.get("COSMO_BENCH_PARITY", "1") != "0":
+    if ctx.world > 1 and args.full and os.environ.get("COSMO_BENCH_PARITY", "1") != "0":
         # parity evidence inside the N > 1 line: a sample of problems FROM EVERY RANK's shard (its first `per`), iterates after warmup + steps
         # iterations, against ONE single-rank batch of exactly those problems run by rank 0 with the same call sequence.  The problems of a batch are
         # independent (src/solver.jl:140-165 per problem, no exchange), so the expected deviation is 0 (bit-identical).
@@ -484,7 +533,7 @@ def bench_cfg3(ctx, args, steps, warmup):
                            lds_bytes_per_krylov_iteration_per_problem=lds_bytes_per_krylov, krylov_iterations_timed=int(kry.sum()),
                            note="LDS bytes of the sparse passes x measured Krylov iterations (device counters) / elapsed; HBM is touched at launch and at the checks "
                                 "only.  The slowest problem's dependent chain of Krylov iterations, not LDS bandwidth, ends the step (see config)")
-    if ctx.world == 1 and os.environ.get("COSMO_BENCH_TTS", "1") != "0":
+    if ctx.world == 1 and args.full and os.environ.get("COSMO_BENCH_TTS", "1") != "0":
         # Time to solution of the whole batch (every problem to the default eps = 1e-5, certificates on) with a tight KKT solve, without and with the
         # reference's default accelerator (AndersonAccelerator, mem 15, safeguarded) running inside the persistent kernels.  Reported, not the metric.
         try:
@@ -726,21 +775,23 @@ def bench_cfg4(ctx, args, steps, warmup):
     st = fixed_work_settings(cj); st.device = ctx.local_rank
     model = cj.Model(); model.set(prob["P"], prob["q"], prob["A"], prob["b"], prob["sets"], st)
     h, elapsed, kbar = _run_sdp(ctx, model, steps, warmup)
+    dump_handle_outputs(ctx, args, model)
     value = whole_job_value(ctx.world, steps, elapsed)
     out = dict(value=value, ms_per_step=1e3 * elapsed / steps, steps=steps, warmup=warmup, scaling="weak")
     if ctx.rank != 0:
         return out
     ps = h.polar_stats()
-    t_prod, fl = h.time_psd_product(0, 20)
-    per_gpu = value / ctx.world
-    out["roofline"] = dict(bound="mfma", kernel="k_symm_gemm<EPI, %d, %d> (symmetric product of the sign iteration, v_mfma_f64_16x16x4_f64)" % (ps["tile_side"], ps["k_split"]),
-                           achieved=round(fl / t_prod / 1e12, 2), peak=F64_MFMA_PEAK_TF, unit="TFLOP/s", frac=round(fl / t_prod / 1e12 / F64_MFMA_PEAK_TF, 4), traffic=None,
-                           peak_sustained_measured=F64_MFMA_SUSTAINED_TF, frac_of_sustained=round(fl / t_prod / 1e12 / F64_MFMA_SUSTAINED_TF, 4),
-                           flops_per_launch=fl, avg_launch_us=round(1e6 * t_prod, 2), launches_timed=20,
-                           products_per_projection=ps["products_last_large"],
-                           performed_tflops_whole_iteration=round(ps["products_last_large"] * fl * per_gpu / 1e12, 2),
-                           useful_tflops_reference_algorithm=round(psd_useful_flops(d) * per_gpu / 1e12, 3),
-                           useful_frac_of_peak=round(psd_useful_flops(d) * per_gpu / 1e12 / F64_MFMA_PEAK_TF, 4))
+    if args.full:
+        t_prod, fl = h.time_psd_product(0, 20)
+        per_gpu = value / ctx.world
+        out["roofline"] = dict(bound="mfma", kernel="k_symm_gemm<EPI, %d, %d> (symmetric product of the sign iteration, v_mfma_f64_16x16x4_f64)" % (ps["tile_side"], ps["k_split"]),
+                               achieved=round(fl / t_prod / 1e12, 2), peak=F64_MFMA_PEAK_TF, unit="TFLOP/s", frac=round(fl / t_prod / 1e12 / F64_MFMA_PEAK_TF, 4), traffic=None,
+                               peak_sustained_measured=F64_MFMA_SUSTAINED_TF, frac_of_sustained=round(fl / t_prod / 1e12 / F64_MFMA_SUSTAINED_TF, 4),
+                               flops_per_launch=fl, avg_launch_us=round(1e6 * t_prod, 2), launches_timed=20,
+                               products_per_projection=ps["products_last_large"],
+                               performed_tflops_whole_iteration=round(ps["products_last_large"] * fl * per_gpu / 1e12, 2),
+                               useful_tflops_reference_algorithm=round(psd_useful_flops(d) * per_gpu / 1e12, 3),
+                               useful_frac_of_peak=round(psd_useful_flops(d) * per_gpu / 1e12 / F64_MFMA_PEAK_TF, 4))
     out["config"] = {"workload": "cfg4: closest-correlation SDP, one PsdConeTriangle d=%d (n=%d, m=%d), CG indirect KKT" % (d, model.n, model.m),
                      "parallelism": "replicas x%d (a single cone does not shard; SURVEY 8e)" % ctx.world,
                      "mean_cg_iters_per_admm_iter": round(kbar, 3), "polar": dict({k: ps[k] for k in ("schedule_steps", "fallback_rounds", "verified", "unverified", "err_max_e18")}, lifting_depth=h.polar_depth_stats())}
@@ -759,7 +810,7 @@ def bench_cfg5(ctx, args, steps, warmup):
     prob = cj.problems.chordal_sdp(**kw)
     st = fixed_work_settings(cj); st.device = ctx.local_rank
     single, share = None, None
-    if ctx.world > 1:
+    if ctx.world > 1 and args.full:
         # self-contained speed-up: rank 0 times the UNSHARDED problem first (the other ranks wait at the barrier inside timed()), and measures
         # which share of that iteration shards
         if ctx.rank == 0:
@@ -775,11 +826,12 @@ def bench_cfg5(ctx, args, steps, warmup):
         ctx.barrier()
     model = cj.Model(); model.set(prob["P"], prob["q"], prob["A"], prob["b"], prob["sets"], st)
     h, elapsed, kbar = _run_sdp(ctx, model, steps, warmup, dist=ctx.dist, shard=args.shard)
+    dump_handle_outputs(ctx, args, model)
     value = steps / elapsed                                                # ONE problem, all ranks work on it: strong scaling
     out = dict(value=value, ms_per_step=1e3 * elapsed / steps, steps=steps, warmup=warmup, scaling="strong")
     rank_seconds = ctx.rank_seconds()
     parity = None
-    if ctx.world > 1 and os.environ.get("COSMO_BENCH_PARITY", "1") != "0":     # (COSMO_BENCH_PARITY=0: throughput only -- for bisecting a failing multi-GPU run)
+    if ctx.world > 1 and args.full and os.environ.get("COSMO_BENCH_PARITY", "1") != "0":     # (COSMO_BENCH_PARITY=0: throughput only -- for bisecting a failing multi-GPU run)
         try:                                                               # a second communicator next to the timed handle's (both stay valid)
             parity = cfg5_sharded_parity_leg(ctx, args, prob)
         except Exception as e:
@@ -807,13 +859,14 @@ def bench_cfg5(ctx, args, steps, warmup):
                                    lifting_depth=h.polar_depth_stats())}
     if ctx.world > 1:
         out["config"]["rank_seconds"] = rank_seconds
-        out["config"]["parity"] = parity
         # the same evidence as FLAT scalars: the driver's parsed copy of the line keeps the scalar entries of `config` (nested objects are dropped there)
         comm = h.bench_comm or {}
-        out["config"]["parity_ok"] = bool(parity and parity.get("ok") and comm.get("selftest") == "ok")
-        out["config"]["parity_sharded_vs_single_max_rel_dev"] = (parity or {}).get("sharded_vs_single_max_rel_dev")
-        out["config"]["parity_expected_at_most"] = 1e-7
-        out["config"]["parity_ranks_bit_identical"] = (parity or {}).get("ranks_bit_identical")
+        if args.full:                                                      # a plain run has no parity leg: no parity verdict either
+            out["config"]["parity"] = parity
+            out["config"]["parity_ok"] = bool(parity and parity.get("ok") and comm.get("selftest") == "ok")
+            out["config"]["parity_sharded_vs_single_max_rel_dev"] = (parity or {}).get("sharded_vs_single_max_rel_dev")
+            out["config"]["parity_expected_at_most"] = 1e-7
+            out["config"]["parity_ranks_bit_identical"] = (parity or {}).get("ranks_bit_identical")
         out["config"]["comm_selftest"] = comm.get("selftest")
         out["config"]["comm_transport"] = comm.get("transport_name")
         out["config"]["comm_rccl_version"] = comm.get("rccl_version")
@@ -832,7 +885,7 @@ def bench_cfg5(ctx, args, steps, warmup):
     # ---- roofline: the kernel class with the largest share of the step's time is named first, the other under `other` ----------------------
     ms_step = 1e3 * elapsed / steps
     products = None
-    if ps["batch_cones"] > 0:
+    if args.full and ps["batch_cones"] > 0:
         # the product kernel timed as the IN-LOOP MIX: per repetition one Y = U^2 and the two alpha A B + beta Cin products of a step of the sign
         # iteration with their real operands (time_psd_product mode 2), not back-to-back launches of the cheapest flavour
         t_prod, fl = h.time_psd_product(2, 20)
@@ -879,7 +932,7 @@ def bench_cfg5(ctx, args, steps, warmup):
                             useful_tflops_reference_algorithm=round(useful * value / 1e12, 3), useful_frac_of_peak=round(useful * value / 1e12 / F64_MFMA_PEAK_TF, 5))
     krylov = None
     pmc5 = None
-    if not args.small:
+    if args.full and not args.small:
         import glob
         for fpmc in sorted(glob.glob(os.path.join(ROOT, "profiles", "r*_cfg5_pmc_traffic.json"))):       # committed PMC passes (constants, like cfg2's)
             try:
@@ -901,7 +954,7 @@ def bench_cfg5(ctx, args, steps, warmup):
             products["traffic_source"] = pmc5[1]
         except Exception:
             pass
-    if ctx.world == 1:
+    if ctx.world == 1 and args.full:
         try:
             t_k, b_k, nl = min(h.time_krylov(200) for _ in range(3))
             fs = h.fold_stats()
@@ -945,10 +998,11 @@ def bench_cfg5(ctx, args, steps, warmup):
         args.deferred.append(cpu_leg)
     if ctx.world == 1:
         h.close()
-        try:
-            out["pcg"] = jacobi_pcg_extra(ctx, args, prob, steps, warmup)
-        except Exception as e:
-            out["pcg"] = dict(error="%s: %s" % (type(e).__name__, e))
+        if args.full:
+            try:
+                out["pcg"] = jacobi_pcg_extra(ctx, args, prob, steps, warmup)
+            except Exception as e:
+                out["pcg"] = dict(error="%s: %s" % (type(e).__name__, e))
         if KKT_CHOICE["name"] == "cg" and not args.no_variants:
             try:
                 out["single_reduction_cg"] = single_reduction_extra(ctx, args, prob, steps, warmup, value, kbar)
@@ -1121,7 +1175,16 @@ def main():
     ap.add_argument("--no-prewarm", action="store_true", help="skip the clock warm-up launches of the product kernel (profiling runs: kernel statistics of the loop's own launches only)")
     ap.add_argument("--exact-launches", action="store_true",
                     help="cfg2: synchronise after every Krylov iteration (rocprofv3 runs: every launch does full work)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: rooflines, cpu_baseline, the other workloads (extra), opt-in variants, Float32, cfg3's time to "
+                         "solution and, at N > 1, the parity leg and the unsharded comparison (a plain run times the headline workload only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write x, y, s of the headline workload (as optimize() returns them) as DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if not args.full:
+        args.no_extra = args.no_cpu_baseline = args.no_variants = args.no_float32 = True
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         relaunch_under_torchrun(args.gpus)                         # does not return
@@ -1153,6 +1216,7 @@ def main():
         head_dog.daemon = True
         head_dog.start()
     res = BENCH[head](ctx, args, args.steps, args.warmup)
+    args.dump_outputs = None                                       # the outputs are the headline's: the extras below must not overwrite them
     if head_dog is not None:
         head_dog.cancel()
     extra = {}

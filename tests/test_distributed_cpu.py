@@ -215,3 +215,32 @@ def test_comm_known_answer_check_combines_the_ranks_verdicts():
     assert bad["selftest"].startswith("FAILED") and bad["exact_sum_mismatches"] == 7
     err = B.comm_known_answer_check(_FakeCtx([(good, None), (None, "RuntimeError: ncclAllReduce failed")]), _FakeHandle(good), 100)
     assert err["selftest"].startswith("FAILED") and "ncclAllReduce" in err["selftest"]
+
+
+def test_bench_dump_outputs_unscales_like_optimize_and_keeps_the_size_cap(tmp_path):
+    """--dump-outputs: x, y, s as optimize() returns them (reverse_scaling!, y = -mu) and, above the size cap, the same seeded sample of
+    positions in every array at every run."""
+    B = _bench_module()
+    n, m = 3, 4
+    sm = cj.model.ScaleMatrices(np.array([2.0, 3.0, 4.0]), np.array([0.5, 1 / 3, 0.25]), np.full(m, 5.0), np.full(m, 0.2), 10.0, 0.1)
+    md = type("Md", (), dict(n=n, settings=cj.Settings(), sm=sm))()
+    w_prev, s, mu = np.arange(1.0, n + m + 1), np.arange(1.0, m + 1), np.arange(2.0, m + 2)
+    a = B.caller_arrays(md, w_prev, s, mu)
+    assert np.array_equal(a["x"], [2.0, 6.0, 12.0]) and np.allclose(a["s"], 0.2 * s) and np.allclose(a["y"], -0.5 * mu)
+    md.settings.scaling = 0
+    a = B.caller_arrays(md, w_prev, s, mu)
+    assert np.array_equal(a["x"], w_prev[:n]) and np.array_equal(a["y"], -mu) and np.array_equal(a["s"], s)
+
+    B.dump_outputs(str(tmp_path / "small"), dict(x=np.arange(5.0), y=np.arange(3, dtype=np.float32), k=np.arange(4)))
+    got = {f: np.load(tmp_path / "small" / (f + ".npy")) for f in ("x", "y", "k")}
+    assert got["x"].dtype == np.float64 and got["y"].dtype == np.float32 and got["k"].dtype == np.float64
+    assert np.array_equal(got["x"], np.arange(5.0)) and np.array_equal(got["k"], np.arange(4.0))
+
+    B.DUMP_LIMIT_BYTES = 8 * 1000                                           # 3000 float64 entries against a cap of 1000
+    big = dict(x=np.arange(1000.0), s=np.arange(2000.0) + 0.5)
+    for run in ("a", "b"):
+        B.dump_outputs(str(tmp_path / run), big)
+    xa, sa = np.load(tmp_path / "a" / "x.npy"), np.load(tmp_path / "a" / "s.npy")
+    assert xa.nbytes + sa.nbytes <= B.DUMP_LIMIT_BYTES and xa.size == 333 and sa.size == 666
+    assert np.all(np.diff(xa) > 0) and np.all(np.isin(sa, big["s"]))        # sorted positions of the original arrays
+    assert np.array_equal(xa, np.load(tmp_path / "b" / "x.npy")) and np.array_equal(sa, np.load(tmp_path / "b" / "s.npy"))

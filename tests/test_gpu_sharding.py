@@ -447,7 +447,7 @@ def test_bench_gpus_8_dry_run_prints_a_well_formed_line_with_parity_evidence():
     and the summary tail.  The committed line of this command is profiles/r06_cfg5_row_sharded_8ranks_one_gpu_dryrun.json."""
     env = dict(os.environ, COSMO_BENCH_TRANSPORT="shm", MASTER_ADDR="127.0.0.1", OMP_NUM_THREADS="2")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "8", "--master-addr", "127.0.0.1", "--master-port", str(_free_port()),
-           os.path.join(ROOT, "bench.py"), "--gpus", "8", "--steps", "6", "--warmup", "2", "--small", "--no-extra", "--no-cpu-baseline"]
+           os.path.join(ROOT, "bench.py"), "--gpus", "8", "--steps", "6", "--warmup", "2", "--small", "--full", "--no-extra", "--no-cpu-baseline"]
     out = _one_json_line(subprocess.run(cmd, env=env, cwd=ROOT, capture_output=True, text=True, timeout=900))
     assert out["n_gpus"] == 8 and out["steps"] == 6 and out["value"] > 0 and out["scaling"] == "strong" and "DRY RUN" in out["data"]
     cfg = out["config"]
@@ -548,7 +548,7 @@ def test_bench_multi_rank_entry_point_dry_run(workload, shard):
     workloads, the MAX-over-ranks timing and the one JSON line of rank 0.  With real GPUs the same code runs over RCCL."""
     env = dict(os.environ, COSMO_BENCH_TRANSPORT="shm", MASTER_ADDR="127.0.0.1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port", str(_free_port()),
-           os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "8", "--warmup", "3", "--small", "--workload", workload, "--shard", shard]
+           os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "8", "--warmup", "3", "--small", "--full", "--workload", workload, "--shard", shard]
     out = _one_json_line(subprocess.run(cmd, env=env, cwd=ROOT, capture_output=True, text=True, timeout=420))
     assert out["n_gpus"] == 2 and out["steps"] == 8 and out["warmup"] == 3 and out["value"] > 0 and out["higher_is_better"] is True
     assert "DRY RUN" in out["data"]
@@ -593,7 +593,7 @@ def test_a_corrupted_exchange_turns_the_bench_lines_parity_evidence_red():
     check and the sharded-vs-single deviation of the SAME bench line must both say so -- a throughput number with a wrong exchange cannot pass."""
     env = dict(os.environ, COSMO_BENCH_TRANSPORT="shm", MASTER_ADDR="127.0.0.1", COSMO_HIP_COMM_CORRUPT_RANK="1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port", str(_free_port()),
-           os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "2", "--small", "--workload", "cfg5", "--shard", "rows"]
+           os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "2", "--small", "--full", "--workload", "cfg5", "--shard", "rows"]
     out = _one_json_line(subprocess.run(cmd, env=env, cwd=ROOT, capture_output=True, text=True, timeout=420))
     comm, par = out["config"]["comm"], out["config"]["parity"]
     assert comm["selftest"].startswith("FAILED") and comm["exact_sum_mismatches"] > 0
@@ -610,7 +610,7 @@ def test_bench_gpus_2_without_a_launcher_is_a_two_rank_run_of_the_same_headline_
     north_star's targets are stated on: ONE problem, unsharded at N = 1, row-sharded at N > 1, `scaling: strong` (the 1 -> 8 curve
     of weak-scaled cfg2 replicas read 8x by construction).  The parity evidence sits at the TOP level of the line; the batch that shards is
     extra.cfg3_sharded; the two configurations that do not shard are explicit replicas, one replica's rate, never aggregated."""
-    common = ["--steps", "6", "--warmup", "2", "--small", "--no-cpu-baseline", "--no-float32"]
+    common = ["--steps", "6", "--warmup", "2", "--small", "--full", "--no-cpu-baseline", "--no-float32"]
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT", "TORCHELASTIC_RUN_ID")}
     one = _one_json_line(subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--no-extra"] + common, env=env, cwd=ROOT,
                                         capture_output=True, text=True, timeout=420))
@@ -649,7 +649,7 @@ def test_bench_reports_the_headline_even_if_a_sharded_extra_never_finishes():
     start -- with what has been collected and ends every rank.  Here the deadline is zero, so it fires while the first extra is being set up."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT", "TORCHELASTIC_RUN_ID")}
     env.update(COSMO_BENCH_TRANSPORT="shm", COSMO_BENCH_EXTRA_TIMEOUT="0.05", COSMO_BENCH_EXTRA_GRACE="1")
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "6", "--warmup", "2", "--small", "--no-cpu-baseline", "--no-float32"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "6", "--warmup", "2", "--small", "--full", "--no-cpu-baseline", "--no-float32"],
                        env=env, cwd=ROOT, capture_output=True, text=True, timeout=600)
     two = _one_json_line(r)
     assert two["n_gpus"] == 2 and two["value"] > 0 and two["config"]["workload"].startswith("cfg5") and two["scaling"] == "strong"
