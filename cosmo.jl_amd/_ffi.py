@@ -23,6 +23,7 @@ EXP, DUAL_EXP, POW, DUAL_POW = 6, 7, 8, 9
 PSD_TRIANGLE_COMPLEX = 10
 CUSTOM = 11
 KKT_CG, KKT_MINRES_REDUCED, KKT_MINRES, KKT_CG_SR, KKT_CG_JACOBI = 0, 1, 2, 3, 4
+KKT_DIRECT = 5          # QdldlKKTSolver: supernodal LDL' of the full KKT matrix on the device (csrc/ldl.hip)
 STATUS_NAMES = {0: "Undetermined", 1: "Solved", 2: "Max_iter_reached", 3: "Unsolved", 4: "Primal_infeasible",
                 5: "Dual_infeasible", 6: "Time_limit_reached"}
 MAT_A, MAT_AT, MAT_P, MAT_OP = 0, 1, 2, 3
@@ -99,6 +100,9 @@ SIGNATURES = {
     "cosmo_hip_cg_persist_stats": (C.c_int32, [C.c_void_p, _PI64]),
     "cosmo_hip_fold_stats": (C.c_int32, [C.c_void_p, _PI64]),
     "cosmo_hip_kkt_recurrence": (C.c_char_p, [C.c_void_p]),
+    "cosmo_hip_ldl_analyze": (C.c_int32, [C.c_int64, C.c_int64, _PI64, _PI64, _PI64, _PI64, _PI64, _PI64]),
+    "cosmo_hip_set_kkt_perm": (C.c_int32, [C.c_void_p, C.c_int64, _PI64]),
+    "cosmo_hip_direct_info": (C.c_int32, [C.c_void_p, _PI64]),
     "cosmo_hip_polar_dataflow_stats": (C.c_int32, [C.c_void_p, _PD]),
     "cosmo_hip_polar_dataflow_reset_timing": (C.c_int32, [C.c_void_p]),
     "cosmo_hip_get_kkt_solution": (C.c_int32, [C.c_void_p, _PR]),
@@ -168,6 +172,26 @@ SIGNATURES = {
 
 def _is_f32(dtype):
     return np.dtype(dtype) == np.float32
+
+
+def ldl_analyze(n, m, P, A, perm=None, dtype=np.float64):
+    """cosmo_hip_ldl_analyze: symbolic analysis of K = [P + sigma I, A'; A, -diag(1 ./ rho)] on the host (no GPU needed).  P, A: scipy sparse
+    (pattern only).  Returns a dict with the eight figures of include/cosmo_hip.h."""
+    import scipy.sparse as sp
+    lib = load_library(dtype)
+    P = sp.csc_matrix(P); A = sp.csc_matrix(A)
+    Pp = P.indptr.astype(np.int64); Pi = P.indices.astype(np.int64)
+    Ap = A.indptr.astype(np.int64); Ai = A.indices.astype(np.int64)
+    pr = None if perm is None else np.ascontiguousarray(perm, dtype=np.int64)
+    if pr is not None and pr.size != n + m:
+        raise ValueError("perm must have n + m = %d entries" % (n + m))
+    out = np.zeros(8, dtype=np.int64)
+    ptr = lambda a: a.ctypes.data_as(_PI64)
+    rc = lib.cosmo_hip_ldl_analyze(int(n), int(m), ptr(Pp), ptr(Pi), ptr(Ap), ptr(Ai), None if pr is None else ptr(pr), ptr(out))
+    if rc != 0:
+        raise CosmoHipError(rc, "cosmo_hip_ldl_analyze failed (bad pattern or permutation)")
+    keys = ["nnz_L", "nnz_stored", "supernodes", "height", "max_width", "amalgamation_zeros", "panel_size", "update_pairs"]
+    return dict(zip(keys, out.tolist()))
 
 
 def load_library(dtype=np.float64):
@@ -453,6 +477,22 @@ class Handle:
         out = np.zeros(8, dtype=np.int64)
         self._chk(self.lib.cosmo_hip_cg_persist_stats(self._h, out.ctypes.data_as(_PI64)))
         return dict(zip(["enabled", "workgroups", "launches", "fallbacks", "tickets", "arrivals", "abort", "lds_per_quarter"], out.tolist()))
+
+    def set_kkt_perm(self, perm):
+        """The ordering of the direct KKT solver (perm[k] = original index at position k, n + m entries); None = the default ordering.
+        Takes effect at the next set_params with KKT_DIRECT."""
+        if perm is None:
+            self._chk(self.lib.cosmo_hip_set_kkt_perm(self._h, 0, None))
+            return
+        p = np.ascontiguousarray(perm, dtype=np.int64)
+        self._chk(self.lib.cosmo_hip_set_kkt_perm(self._h, int(p.size), p.ctypes.data_as(_PI64)))
+
+    def direct_info(self):
+        """Figures of the direct KKT solver (cosmo_hip_direct_info)."""
+        out = np.zeros(8, dtype=np.int64)
+        self._chk(self.lib.cosmo_hip_direct_info(self._h, out.ctypes.data_as(_PI64)))
+        keys = ["nnz_L", "nnz_stored", "supernodes", "height", "max_width", "factorizations", "positive_pivots", "last_factor_ns"]
+        return dict(zip(keys, out.tolist()))
 
     def kkt_recurrence(self):
         """Which Krylov recurrence / kernels the KKT solves of this handle run (cosmo_hip_kkt_recurrence)."""

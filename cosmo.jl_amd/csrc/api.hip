@@ -257,6 +257,7 @@ extern "C" int32_t cosmo_hip_destroy(cosmo_hip_handle* h) {
   if (h->stream) (void)hipStreamSynchronize(h->stream);
   free_csr(h->A); free_csr(h->AT); free_csr(h->P); free_csr(h->PT);
   free_op_split(h);
+  ldl_free(h);
   pcg_free(h);
   sr_free(h);
   (void)cosmo_hip_comm_destroy(h);
@@ -314,6 +315,7 @@ extern "C" int32_t cosmo_hip_set_problem(cosmo_hip_handle* h, int64_t n, int64_t
   }
   PT.rowptr[n] = (int)p;
   free_op_split(h);
+  ldl_free(h);                       // the factor's analysis belongs to the old pattern
   CHK(upload_csr(h, Am, h->A, (int)n));
   CHK(upload_csr(h, At, h->AT, (int)m));
   CHK(upload_csr(h, Pm, h->P, (int)n));
@@ -592,7 +594,7 @@ extern "C" int32_t cosmo_hip_set_params(cosmo_hip_handle* h, const cosmo_hip_par
   if (h->row_shard) return cosmo_fail(h, COSMO_HIP_ERR_UNSUPPORTED, "set_params: not available on a row-sharded handle");
   if (!p) return cosmo_fail(h, COSMO_HIP_ERR_INVALID, "null params");
   if (!h->have_cones) return cosmo_fail(h, COSMO_HIP_ERR_INVALID, "set_cones must be called before set_params");
-  if (p->kkt_kind < COSMO_HIP_KKT_CG || p->kkt_kind > COSMO_HIP_KKT_CG_JACOBI) return cosmo_fail(h, COSMO_HIP_ERR_INVALID, "bad kkt_kind");
+  if (p->kkt_kind < COSMO_HIP_KKT_CG || p->kkt_kind > COSMO_HIP_KKT_DIRECT) return cosmo_fail(h, COSMO_HIP_ERR_INVALID, "bad kkt_kind");
   if (p->check_termination <= 0) return cosmo_fail(h, COSMO_HIP_ERR_INVALID, "check_termination must be > 0");
   if (p->adaptive_rho && p->adaptive_rho_interval == 0 && !(p->adaptive_rho_fraction >= 0.0 && p->setup_time >= 0.0))
     return cosmo_fail(h, COSMO_HIP_ERR_INVALID, "adaptive_rho_interval == 0 needs adaptive_rho_fraction >= 0 and setup_time >= 0");
@@ -619,7 +621,7 @@ extern "C" int32_t cosmo_hip_set_params(cosmo_hip_handle* h, const cosmo_hip_par
   h->ctl_host->kkt_iters_total = 0;
   CHK(h2d(h, h->ctl, h->ctl_host, 1));
   h->host_solves = 0;
-  if (h->prm.kkt_kind != COSMO_HIP_KKT_CG) CHK(minres_alloc(h));
+  if (h->prm.kkt_kind != COSMO_HIP_KKT_CG && h->prm.kkt_kind != COSMO_HIP_KKT_DIRECT) CHK(minres_alloc(h));
   CHK(sr_alloc(h));
   // the Krylov warm start (previous_solution) starts at zero (kktsolver_indirect.jl:32)
   HIPCHK(h, hipMemsetAsync(h->x_tl, 0, sizeof(real) * (size_t)std::max<long long>(h->n, 1), h->stream));
@@ -633,6 +635,16 @@ extern "C" int32_t cosmo_hip_set_params(cosmo_hip_handle* h, const cosmo_hip_par
     if (fuse) CHK(dalloc(h, &h->cg_ru, 2 * (size_t)h->n)); }
   CHK(build_op_split(h));     // needs the (scaled) matrices and rho: both final from here on
   CHK(choose_cg_recurrence(h));
+  if (h->prm.kkt_kind == COSMO_HIP_KKT_DIRECT) {
+    // QdldlKKTSolver (kktsolver.jl:285-307): analysis (kept while the pattern and the requested ordering stay), factorisation, inertia check
+    h->pcg_on = false;
+    const int32_t rc = ldl_setup(h, h->kkt_perm);
+    // no usable factor (failed analysis or allocation, zero pivot, wrong inertia): solves, update_rho and optimize refuse until a set_params
+    // succeeds.  The plan's figures stay readable through cosmo_hip_direct_info (positive pivots of the refused factor).
+    if (rc != COSMO_HIP_OK) { h->have_params = false; h->have_iterates = false; }
+    return rc;
+  }
+  ldl_free(h);
   if (h->cg_jacobi) {
     // the opt-in Jacobi-preconditioned CG lives on the ASSEMBLED reduced operator (its diagonal is the preconditioner): no silent fallback to the
     // unpreconditioned recurrence when the operator cannot be assembled (dense A' rho A: BASELINE config 2, where Jacobi makes the count worse anyway)
@@ -653,7 +665,31 @@ extern "C" int32_t cosmo_hip_update_rho(cosmo_hip_handle* h, const real* rho_vec
   if (h->row_shard) return cosmo_fail(h, COSMO_HIP_ERR_UNSUPPORTED, "update_rho: not available on a row-sharded handle");
   if (!h->have_params || !rho_vec) return cosmo_fail(h, COSMO_HIP_ERR_INVALID, "update_rho: not set up");
   CHK(h2d(h, h->rho, rho_vec, (size_t)h->m));
+  if (h->prm.kkt_kind == COSMO_HIP_KKT_DIRECT) {          // update_rho!(::QdldlKKTSolver): new values, refactor (:316-320)
+    const int32_t rc = ldl_refactor_now(h, false);
+    if (rc != COSMO_HIP_OK) { h->have_params = false; h->have_iterates = false; }    // a zero pivot leaves no usable factor
+    return rc;
+  }
   return refresh_op_split(h);
+}
+
+extern "C" int32_t cosmo_hip_set_kkt_perm(cosmo_hip_handle* h, int64_t len, const int64_t* perm) {
+  ENTER(h);
+  if (!perm) { h->kkt_perm.clear(); return COSMO_HIP_OK; }
+  if (!h->have_problem || len != h->n + h->m) return cosmo_fail(h, COSMO_HIP_ERR_INVALID, "set_kkt_perm: the permutation must have n + m entries (set_problem first)");
+  std::vector<char> seen((size_t)len, 0);
+  for (int64_t k = 0; k < len; ++k) {
+    if (perm[k] < 0 || perm[k] >= len || seen[perm[k]]) return cosmo_fail(h, COSMO_HIP_ERR_INVALID, "set_kkt_perm: not a permutation of 0 .. n+m-1");
+    seen[perm[k]] = 1;
+  }
+  h->kkt_perm.assign(perm, perm + len);
+  return COSMO_HIP_OK;
+}
+
+extern "C" int32_t cosmo_hip_direct_info(cosmo_hip_handle* h, int64_t* out) {
+  ENTER(h);
+  if (!out) return cosmo_fail(h, COSMO_HIP_ERR_INVALID, "direct_info: null output");
+  return ldl_info(h, out);
 }
 
 static int32_t upload_or_ones(cosmo_hip_handle* h, real* dst, const real* src, size_t n) {
@@ -841,6 +877,8 @@ extern "C" int32_t cosmo_hip_kkt_solve(cosmo_hip_handle* h, real* lhs, const rea
     }
     CHK(enqueue_tail(h, 0));
     CHK(enqueue_count_solve(h));
+  } else if (h->prm.kkt_kind == COSMO_HIP_KKT_DIRECT) {
+    CHK(ldl_enqueue_solve(h, 0, false));          // the full (n+m) system, as solve!(::QdldlKKTSolver) (kktsolver.jl:310-313)
   } else {
     CHK(minres_enqueue_solve(h, 0, false));
   }
@@ -970,6 +1008,8 @@ static int32_t enqueue_solve_in_loop(cosmo_hip_handle* h) {
     }
     CHK(enqueue_tail(h, 1));
     CHK(feedback_record(h));
+  } else if (h->prm.kkt_kind == COSMO_HIP_KKT_DIRECT) {
+    CHK(ldl_enqueue_solve(h, 1, true));
   } else {
     CHK(minres_enqueue_solve(h, 1, true));
   }
@@ -1504,6 +1544,7 @@ extern "C" const char* cosmo_hip_kkt_recurrence(cosmo_hip_handle* h) {
   static const char* pc_names[] = {"", "k_cg_dirM<1, true> + k_cg_upd<true>", "k_cg_dirM<2, true> + k_cg_upd<true>", "k_cg_dirM<3, true> + k_cg_upd<true>",
                                    "k_cg_dirM<4, true> + k_cg_upd<true>", "", "", "", "k_cg_dirM<8, true> + k_cg_upd<true>"};
   static thread_local char buf[256];
+  if (h->prm.kkt_kind == COSMO_HIP_KKT_DIRECT) return "direct: supernodal LDL' of the full KKT system, one launch per tree level (csrc/ldl.hip)";
   if (h->prm.kkt_kind == COSMO_HIP_KKT_MINRES) return "minres on the full KKT system (csrc/minres.hip)";
   if (h->prm.kkt_kind == COSMO_HIP_KKT_MINRES_REDUCED) return "minres on the reduced system (csrc/minres.hip)";
   const FoldPlan* f = (const FoldPlan*)h->fold;

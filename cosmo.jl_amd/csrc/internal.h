@@ -269,6 +269,9 @@ struct cosmo_hip_handle {
   double kc_seconds[COSMO_HIP_NUM_KERNEL_CLASSES] = {0};
   long long kc_launches[COSMO_HIP_NUM_KERNEL_CLASSES] = {0};
   hipEvent_t ev_proj0 = nullptr, ev_proj1 = nullptr;
+  // direct KKT solver (ldl.hip): the supernodal factor, built by set_params for kkt_kind COSMO_HIP_KKT_DIRECT
+  void* ldl = nullptr;            // LdlPlan
+  std::vector<int64_t> kkt_perm;  // cosmo_hip_set_kkt_perm (empty: the default ordering)
 };
 
 // ---- error handling ------------------------------------------------------------------------------------------------
@@ -319,6 +322,14 @@ int32_t enqueue_admm_x_and_w(cosmo_hip_handle* h);
 int32_t sync_ctl(cosmo_hip_handle* h);
 
 int32_t comm_allreduce_flag(cosmo_hip_handle* h, int* flag);   // comm.hip: max over the ranks of a 0/1 flag
+
+// direct KKT solver (ldl.hip)
+int32_t ldl_setup(cosmo_hip_handle* h, const std::vector<int64_t>& perm_req);
+void ldl_free(cosmo_hip_handle* h);
+int32_t ldl_enqueue_refactor(cosmo_hip_handle* h, int cond);    // cond = 1: only if Ctl::rho_changed (the loop)
+int32_t ldl_refactor_now(cosmo_hip_handle* h, bool inertia);
+int32_t ldl_enqueue_solve(cosmo_hip_handle* h, int guard, bool from_loop);
+int32_t ldl_info(cosmo_hip_handle* h, int64_t* out);
 
 // single-reduction CG (cg_sr.hip)
 int32_t sr_alloc(cosmo_hip_handle* h);

@@ -970,6 +970,7 @@ int32_t enqueue_check(cosmo_hip_handle* h, int guard, int mode) {
       hipLaunchKernelGGL(k_rs_rho_g, dim3(ew_grid(h->m_g > 0 ? h->m_g : 1)), dim3(COSMO_BS), 0, h->stream, h->ctl, guard, h->m_g, h->rho_cls_g,
                          h->prm.rho_min, h->prm.rho_eq_over_rho_ineq, h->rho_g);
     CHK(refresh_op_split(h));      // rho may have changed on the device: the diagonal part of A' rho A follows (cheap, unconditional)
+    if (h->ldl) CHK(ldl_enqueue_refactor(h, 1));   // direct KKT solver: refill + refactorise, each launch a no-op unless rho changed
     prof_end(h);
   }
   h->spmv_calls[0] += 1; h->spmv_calls[1] += 1; h->spmv_calls[2] += 1;

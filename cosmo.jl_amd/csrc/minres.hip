@@ -349,6 +349,16 @@ static int32_t enqueue_mr_tail(cosmo_hip_handle* h, int loop_mode) {
   return enqueue_tail(h, loop_mode);
 }
 
+// the full-KKT tail on a solution computed elsewhere (the direct solver, ldl.hip)
+int32_t launch_mr_tail_full(cosmo_hip_handle* h, int loop_mode, const real* xsol) {
+  prof_begin(h, KC_TAIL);
+  hipLaunchKernelGGL(k_mr_tail_full, dim3(ewg(h->n + h->m)), dim3(COSMO_BS), 0, h->stream, h->ctl, loop_mode, h->n, h->m, h->prm.alpha,
+                     xsol, h->rho, h->s, h->x_tl, h->nu, h->s_tl, h->w);
+  prof_end(h);
+  HIPCHK(h, hipGetLastError());
+  return COSMO_HIP_OK;
+}
+
 int32_t minres_resume(cosmo_hip_handle* h, int extra) {
   CHK(minres_enqueue_iterations(h, 1, h->ctl_host->cg_k + 1, extra));
   return enqueue_mr_tail(h, 1);

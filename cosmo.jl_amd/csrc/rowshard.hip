@@ -72,6 +72,9 @@ extern "C" int32_t cosmo_hip_set_row_shard(cosmo_hip_handle* h, const int64_t* f
   if (hipSetDevice(h->device) != hipSuccess) return cosmo_fail(h, COSMO_HIP_ERR_HIP, "hipSetDevice failed");
   if (!h->have_params) return cosmo_fail(h, COSMO_HIP_ERR_INVALID, "set_row_shard: set_params first (the reduced operator is built from the whole A)");
   if (h->row_shard) return cosmo_fail(h, COSMO_HIP_ERR_INVALID, "set_row_shard: already row-sharded");
+  if (h->prm.kkt_kind == COSMO_HIP_KKT_DIRECT)
+    return cosmo_fail(h, COSMO_HIP_ERR_UNSUPPORTED, "set_row_shard: the direct KKT solver (kkt_kind DIRECT) factorises the whole KKT matrix on one device; "
+                      "a sharded factorisation is not implemented");
   if (h->prm.kkt_kind != COSMO_HIP_KKT_CG && h->prm.kkt_kind != COSMO_HIP_KKT_MINRES_REDUCED)
     return cosmo_fail(h, COSMO_HIP_ERR_UNSUPPORTED, "set_row_shard: the solvers of the REDUCED system only (kkt_kind CG / CG_SR / CG_JACOBI / MINRES_REDUCED); "
                       "MINRES on the full KKT system would need an all-reduce per operator application");

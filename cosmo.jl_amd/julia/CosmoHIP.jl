@@ -27,6 +27,7 @@ libpath(::Type{Float32}) = LIB32[]
 include("abi_structs.jl")
 
 const KKT_CG, KKT_MINRES_REDUCED, KKT_MINRES, KKT_CG_SR, KKT_CG_JACOBI = Int32(0), Int32(1), Int32(2), Int32(3), Int32(4)   # KKT_CG_SR: opt-in single-reduction CG; KKT_CG_JACOBI: opt-in Jacobi-preconditioned CG (assembled operator only)
+const KKT_DIRECT = Int32(5)   # QdldlKKTSolver on the device: supernodal LDL' of the full KKT matrix (csrc/ldl.hip)
 const STATUS = (:Undetermined, :Solved, :Max_iter_reached, :Unsolved, :Primal_infeasible, :Dual_infeasible, :Time_limit_reached)
 
 # the struct mirrors of abi_structs.jl were generated for ABI_VERSION: a library that reports another version would read / write them with a
@@ -232,6 +233,9 @@ HipMINRESKKTSolver(P, A, sigma, rho; kwargs...) = HipKKTSolver(P, A, sigma, rho;
 # OPT-IN, no reference counterpart (COSMO calls cg! without a preconditioner, src/linear_solver/kktsolver_indirect.jl:70): IterativeSolvers' preconditioned
 # recurrence with Pl = Diagonal(diag(P + sigma I + A' rho A)); set_params! fails where the reduced operator cannot be assembled
 HipCGJacobiKKTSolver(P, A, sigma, rho; kwargs...) = HipKKTSolver(P, A, sigma, rho; kind = KKT_CG_JACOBI, kwargs...)
+# QdldlKKTSolver (src/linear_solver/kktsolver.jl:285-320) on the device: set_params! analyses, factorises and throws "Objective function is not
+# convex." for a non-convex P; solve! solves the full (n+m) system, update_rho! refactorises
+HipQdldlKKTSolver(P, A, sigma, rho; kwargs...) = HipKKTSolver(P, A, sigma, rho; kind = KKT_DIRECT, kwargs...)
 
 # called from admm_x! (src/solver.jl:52): lhs = ws.sol, rhs = ws.ls, both length n+m and caller owned
 function solve!(S::HipKKTSolver{T}, lhs::AbstractVector{T}, rhs::AbstractVector{T}) where {T <: HipFloat}

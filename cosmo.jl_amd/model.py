@@ -34,7 +34,7 @@ QdldlKKTSolver = "QdldlKKTSolver"
 CGSingleReductionKKTSolver = "CGSingleReductionKKTSolver"
 # opt-in, no reference counterpart: Jacobi-preconditioned CG (IterativeSolvers' PCGIterable, Pl = diag of the reduced operator) on the assembled operator, csrc/cg_fold.hip
 CGJacobiKKTSolver = "CGJacobiKKTSolver"
-_KKT_KIND = {CGIndirectKKTSolver: _ffi.KKT_CG, MINRESIndirectKKTSolver: _ffi.KKT_MINRES, CGSingleReductionKKTSolver: _ffi.KKT_CG_SR, CGJacobiKKTSolver: _ffi.KKT_CG_JACOBI,
+_KKT_KIND = {QdldlKKTSolver: _ffi.KKT_DIRECT, CGIndirectKKTSolver: _ffi.KKT_CG, MINRESIndirectKKTSolver: _ffi.KKT_MINRES, CGSingleReductionKKTSolver: _ffi.KKT_CG_SR, CGJacobiKKTSolver: _ffi.KKT_CG_JACOBI,
              IndirectReducedKKTSolverMINRES: _ffi.KKT_MINRES_REDUCED}
 
 
@@ -656,12 +656,13 @@ def _params_from_settings(h, st: Settings):
     if isinstance(kkt, OptionsFactory):
         kw = kkt.kwargs
         kkt = kkt.solver
-    if kkt == QdldlKKTSolver:
-        raise NotImplementedError("QdldlKKTSolver is the reference's CPU direct solver (config 1, plumbing only); "
-                                  "the MI355X path provides CGIndirectKKTSolver / MINRESIndirectKKTSolver")
     if kkt not in _KKT_KIND:
         raise ValueError("unknown kkt_solver %r" % (kkt,))
     p.kkt_kind = _KKT_KIND[kkt]
+    if kkt == QdldlKKTSolver:
+        # the device LDL' (csrc/ldl.hip); with_options(QdldlKKTSolver, perm=...) supplies the ordering (perm[k] = original index at position k)
+        if h is not None:
+            h.set_kkt_perm(kw.get("perm"))
     p.tol_constant = float(kw.get("tol_constant", 1.0))
     p.tol_exponent = float(kw.get("tol_exponent", 1.5))
     p.sigma, p.alpha, p.rho = st.sigma, st.alpha, st.rho
@@ -809,6 +810,9 @@ def optimize(model: Model, dist=None, shard: str = "rows") -> Result:
     if dist is not None and dist.get_world_size() > 1 and fresh:
         kkt = model.settings.kkt_solver.solver if isinstance(model.settings.kkt_solver, OptionsFactory) else model.settings.kkt_solver
         rows_ok = kkt in (CGIndirectKKTSolver, CGSingleReductionKKTSolver, CGJacobiKKTSolver, IndirectReducedKKTSolverMINRES)
+        if kkt == QdldlKKTSolver:
+            raise NotImplementedError("QdldlKKTSolver on more than one device: a sharded factorisation is not implemented; "
+                                      "solve with one process, or use CGIndirectKKTSolver")
         if shard == "rows" and rows_ok:
             setup_row_sharding(model, dist)
         else:

@@ -96,6 +96,12 @@ enum {
                                        and true-residual stopping rule ||r||_2 <= tol_k / ||rhs||, DIFFERENT iterates (every solve ends at another
                                        point inside the same tolerance).  cosmo_hip_set_params fails with UNSUPPORTED where the operator cannot be
                                        assembled (csrc/cg_fold.hip).  Never the parity path. */
+  ,
+  COSMO_HIP_KKT_DIRECT = 5          /* QdldlKKTSolver (src/linear_solver/kktsolver.jl:285-320, the reference's default): LDL' of the quasi-definite
+                                       K = [P + sigma I, A'; A, -diag(1 ./ rho)] under a fill-reducing symmetric permutation, refactorised when rho
+                                       changes, inertia-checked at setup ("Objective function is not convex.").  Supernodal and left-looking on the
+                                       device (csrc/ldl.hip), symbolic analysis on the host (csrc/ldl_symbolic.cpp).  Opt-in; single-problem,
+                                       unsharded handles only */
 };
 
 /* ---- solver status (Result.status symbols, src/solver.jl:113,175,312,318,338,344,353) -------------- */
@@ -325,6 +331,21 @@ COSMO_HIP_API int32_t cosmo_hip_fold_stats(cosmo_hip_handle* h, int64_t out[6]);
  * "cg: literal recurrence on the assembled operator, two launches per iteration, k_cg_dirM<3, false> + k_cg_upd<false>"): bench.py's
  * config.kkt_solver and roofline.kernel. */
 COSMO_HIP_API const char* cosmo_hip_kkt_recurrence(cosmo_hip_handle* h);
+
+/* ---- direct KKT solver (kkt_kind COSMO_HIP_KKT_DIRECT, csrc/ldl.hip) ---- */
+/* Symbolic analysis of K's pattern alone, on the host (no handle, no device).  P: n x n CSC (its upper triangle is used, as
+ * assemble_kkt_triangle(P, A, sigma, rho, :U)), A: m x n CSC, both 0-based.  perm: NULL = the default ordering (rows of A with at most one entry
+ * first, then approximate minimum degree on the rest), else perm[k] = original index at position k (a permutation of n + m).  out = {nnz(L)
+ * strictly below the diagonal without amalgamation zeros, entries stored below the diagonal, supernodes, height of the supernodal tree (levels),
+ * widest supernode, amalgamation zeros, panel values allocated on the device, left-looking update pairs}. */
+COSMO_HIP_API int32_t cosmo_hip_ldl_analyze(int64_t n, int64_t m, const int64_t* P_colptr, const int64_t* P_rowval, const int64_t* A_colptr,
+                                            const int64_t* A_rowval, const int64_t* perm, int64_t out[8]);
+/* The ordering the next cosmo_hip_set_params with kkt_kind DIRECT analyses with (len = n + m, convention of cosmo_hip_ldl_analyze); NULL = the
+ * default ordering.  Call after set_problem. */
+COSMO_HIP_API int32_t cosmo_hip_set_kkt_perm(cosmo_hip_handle* h, int64_t len, const int64_t* perm);
+/* out = {nnz(L), entries stored, supernodes, tree height, widest supernode, factorisations so far (setup, update_rho and in-loop refactorisations),
+ * positive pivots of the last factorisation, wall time of the last factorisation outside the loop in ns}.  kkt_kind DIRECT only. */
+COSMO_HIP_API int32_t cosmo_hip_direct_info(cosmo_hip_handle* h, int64_t out[8]);
 /* Statistics of the device loop since set_iterates: out = {admm_iters, kkt_solves, kkt_iters_total,
  * kkt_budget_stalls, spmv_A_calls, spmv_AT_calls, spmv_P_calls, rho_updates}. */
 COSMO_HIP_API int32_t cosmo_hip_get_stats(cosmo_hip_handle* h, int64_t out[8]);
