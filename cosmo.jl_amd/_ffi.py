@@ -150,6 +150,9 @@ SIGNATURES = {
     "cosmo_hip_batch_get_iterates": (C.c_int32, [C.c_void_p, C.c_int64, _PR, _PR, _PR, _PR]),
     "cosmo_hip_batch_get_counters": (C.c_int32, [C.c_void_p, _PI64]),
     "cosmo_hip_batch_kernel_info": (C.c_int32, [C.c_void_p, _PI64]),
+    "cosmo_hip_batch_set_direct": (C.c_int32, [C.c_void_p, C.c_int32, _PI64]),
+    "cosmo_hip_batch_direct_info": (C.c_int32, [C.c_void_p, _PI64]),
+    "cosmo_hip_batch_direct_counts": (C.c_int32, [C.c_void_p, _PI64]),
     "cosmo_hip_batch_group_create": (C.c_int32, [C.POINTER(C.c_void_p), C.c_int32, C.c_int64]),
     "cosmo_hip_batch_group_destroy": (C.c_int32, [C.c_void_p]),
     "cosmo_hip_batch_group_last_error": (C.c_char_p, [C.c_void_p]),
@@ -158,6 +161,7 @@ SIGNATURES = {
     "cosmo_hip_batch_group_set_scaling": (C.c_int32, [C.c_void_p, C.c_int64, _PR, _PR, C.c_double]),
     "cosmo_hip_batch_group_set_scaling_full": (C.c_int32, [C.c_void_p, C.c_int64, _PR, _PR, _PR, _PR, C.c_double, C.c_double]),
     "cosmo_hip_batch_group_set_accelerator": (C.c_int32, [C.c_void_p, C.POINTER(AccelParams)]),
+    "cosmo_hip_batch_group_set_direct": (C.c_int32, [C.c_void_p, C.c_int32]),
     "cosmo_hip_batch_group_set_params": (C.c_int32, [C.c_void_p, C.POINTER(Params)]),
     "cosmo_hip_batch_group_class_info": (C.c_int32, [C.c_void_p, _PI64, _PI64, _PI64]),
     "cosmo_hip_batch_group_run_info": (C.c_int32, [C.c_void_p, _PI64]),
@@ -689,6 +693,30 @@ class Batch:
             ap.start_accuracy = float(start_accuracy)
         self._chk(self.lib.cosmo_hip_batch_set_accelerator(self._b, C.byref(ap)))
 
+    def set_direct(self, on=True, perm=None):
+        """cosmo_hip_batch_set_direct: the next set_params takes kkt_kind DIRECT (one LDL' per problem, one analysis for the batch); before set_params.
+        perm: None = the default ordering, else n + m entries (perm[k] = original index at position k)."""
+        if perm is None:
+            self._chk(self.lib.cosmo_hip_batch_set_direct(self._b, 1 if on else 0, None))
+            return
+        p = np.ascontiguousarray(perm, dtype=np.int64)
+        if p.size != self.n + self.m:
+            raise ValueError("perm needs n + m = %d entries" % (self.n + self.m))
+        self._chk(self.lib.cosmo_hip_batch_set_direct(self._b, 1 if on else 0, p.ctypes.data_as(_PI64)))
+
+    def direct_info(self):
+        """Figures of the batch's direct KKT solver (cosmo_hip_batch_direct_info)."""
+        out = np.zeros(8, dtype=np.int64)
+        self._chk(self.lib.cosmo_hip_batch_direct_info(self._b, out.ctypes.data_as(_PI64)))
+        keys = ("nnz_L", "panel_size", "supernodes", "height", "max_width", "analysis_ns", "factorizations", "min_positive_pivots")
+        return dict(zip(keys, (int(v) for v in out)))
+
+    def direct_counts(self):
+        """Factorisations of every member so far, the set-up one included (int64 array of nprob)."""
+        out = np.zeros(self.nprob, dtype=np.int64)
+        self._chk(self.lib.cosmo_hip_batch_direct_counts(self._b, out.ctypes.data_as(_PI64)))
+        return out
+
     def accel_stats(self):
         """Per problem: dict of int64 arrays (accelerated, accepted, declined, restarts, active, safeguarding_iter)."""
         out = np.zeros(6 * self.nprob, dtype=np.int64)
@@ -802,6 +830,10 @@ class BatchGroup:
         if start_accuracy is not None:
             ap.start_accuracy = float(start_accuracy)
         self._chk(self.lib.cosmo_hip_batch_group_set_accelerator(self._g, C.byref(ap)))
+
+    def set_direct(self, on=True):
+        """cosmo_hip_batch_group_set_direct: every class's batch takes kkt_kind DIRECT (default ordering); before set_params."""
+        self._chk(self.lib.cosmo_hip_batch_group_set_direct(self._g, 1 if on else 0))
 
     def set_params(self, params):
         self._chk(self.lib.cosmo_hip_batch_group_set_params(self._g, C.byref(params)))

@@ -15,6 +15,8 @@
 // Accelerator (round 4): with cosmo_hip_batch_set_accelerator the loop is the reference's accelerated loop (src/solver.jl:140-165,
 // src/accelerator_interface.jl:58-116) per problem -- Anderson update / accelerate, safeguarding, deferred rho updates and certificates -- all inside
 // the persistent workgroup (aa_pre / aa_declined / aa_reset below, shared by batch_admm_body and k_batch_admm_reg through an element visitor).
+// Direct KKT solver (opt-in, cosmo_hip_batch_set_direct): k_batch_admm_direct, the streaming form with the LDL' solve and the in-workgroup
+// refactorisation of batch_ldl.h (one analysis of the union of the members' patterns, one factor slab per problem).
 #include <stdarg.h>
 #include <stdlib.h>
 #include <string.h>
@@ -25,6 +27,7 @@
 #include "psd16.h"
 #include "psdwg.h"
 #include "cone3.h"
+#include "batch_ldl.h"
 
 struct BCtl {                 // per problem, device resident
   int status; int n_rho_updates;
@@ -80,6 +83,7 @@ struct BatchDev {
   // pdiag: P is diagonal in every problem of the batch and lives in registers (nprob * n, 0 where a row of P is empty; pdiag_has: 1 where it has its entry)
   const uint32_t *slA, *slT; const real* pdiag; const unsigned char* pdiag_has; int sliced;
   int regcg;                    // LDS-image kernel with the extended cones (512 threads): Krylov vectors in registers (n <= 1024, m <= 2048; batch_admm_body)
+  BLdlDev ldl;                  // direct KKT solver (cosmo_hip_batch_set_direct; batch_ldl.h): read by the DIR instantiations only
 };
 
 struct BParams {
@@ -754,7 +758,8 @@ __device__ __forceinline__ void aa_reset(const AaMem& M, Each each) {
 #ifndef COSMO_LDSCG_HANDPIPE
 #define COSMO_LDSCG_HANDPIPE 1          // lab builds: 0 = the compiled one-stage pipelined row loops in the register-CG form of the LDS-image kernel
 #endif
-template <int BS, bool PSD, bool AA, class Ops>
+// DIR: the KKT systems are solved by the problem's own LDL' factor (batch_ldl.h) instead of CG; streaming form only (k_batch_admm_direct).
+template <int BS, bool PSD, bool AA, class Ops, bool DIR = false>
 __device__ __forceinline__ void batch_admm_body(const BatchDev& D, const BParams& P, long long iter_target, int do_init, Ops& ops, real* red, const int k) {
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
   const int n = D.n, m = D.m;
@@ -904,6 +909,12 @@ __device__ __forceinline__ void batch_admm_body(const BatchDev& D, const BParams
     }
   };
   auto solve_and_update = [&]() {
+    if constexpr (DIR) {                                                 // solve!(::QdldlKKTSolver) + the full-KKT tail; no Krylov iterations
+      bldl_solve<BS>(D.ldl, k, n, P.sigma, P.alpha, w, s, q, b, rho, x_tl, nu, s_tl);
+      if (tid == 0) ctl->solves += 1;
+      __syncthreads();
+      return;
+    }
     if constexpr (RCG) { if (D.regcg != 0) { solve_and_update_rcg(); return; } }
     for (int i = tid; i < n + m; i += BS) {                             // rhs of the KKT system + y2 = rho .* ls_s
       if (i < n) ls_x[i] = P.sigma * w[i] - q[i];
@@ -1068,6 +1079,15 @@ __device__ __forceinline__ void batch_admm_body(const BatchDev& D, const BParams
           ctl->n_rho_updates = ku + 1;
         }
         if constexpr (AA) { S.iter = 0; S.init = 1; }                     // CA.restart! (solver.jl:272-275): the operator changed
+        if constexpr (DIR) {                                              // update_rho!(::QdldlKKTSolver) (kktsolver.jl:316-320): this problem only
+          const long long po = D.PT.nz_off[k], ao = D.A.nz_off[k];
+          if (bldl_refill_factor<BS>(D.ldl, k, n, m, P.sigma, D.PT.val + po, D.PT.rowptr[(long long)k * (n + 1) + n], D.A.val + ao,
+                                     D.A.rowptr[(long long)k * (m + 1) + m], rho, po, ao)) {
+            if (tid == 0) ctl->status = COSMO_HIP_UNSOLVED;               // a zero / non-finite pivot: the problem stops, batch_optimize reports it
+            __syncthreads();
+            break;
+          }
+        }
       }
       __syncthreads();
     }
@@ -1131,6 +1151,19 @@ __global__ __launch_bounds__(COSMO_BS) void k_batch_admm(BatchDev D, BParams P, 
   StreamOps ops;
   ops.A = bview(D.A, k); ops.AT = bview(D.AT, k); ops.PT = bview(D.PT, k); ops.lds = lds; ops.red = red; ops.psd_ws = psd_ws;
   batch_admm_body<COSMO_BS, PSD, AA>(D, P, iter_target, do_init, ops, red, k);
+}
+
+// the direct KKT solver (cosmo_hip_batch_set_direct): the streaming form with the LDL' solve of batch_ldl.h
+template <bool PSD, bool AA>
+__global__ __launch_bounds__(COSMO_BS) void k_batch_admm_direct(BatchDev D, BParams P, long long iter_target, int do_init) {
+  __shared__ real lds[COSMO_NNZ_PER_BLOCK];
+  __shared__ real red[COSMO_BS / 64];
+  __shared__ __attribute__((aligned(16))) unsigned char psd_ws[PSD ? (COSMO_BS / 64) * PSD16_WS_STRIDE : 16];
+  const int k = blockIdx.x;
+  if (D.ctl[k].status != 0) return;
+  StreamOps ops;
+  ops.A = bview(D.A, k); ops.AT = bview(D.AT, k); ops.PT = bview(D.PT, k); ops.lds = lds; ops.red = red; ops.psd_ws = psd_ws;
+  batch_admm_body<COSMO_BS, PSD, AA, StreamOps, true>(D, P, iter_target, do_init, ops, red, k);
 }
 
 // MERGED launch over one-problem batches of DIFFERENT structure (batch_multi_optimize): the streaming form takes any size and reads everything it needs
@@ -2203,6 +2236,8 @@ struct cosmo_hip_batch {
   std::vector<int> h_qposA;                   // per problem: position of row i of A in the image's (sorted) storage order
   // sliced image of the register kernel (build_lds_images): first entry | length << 16 of every thread's rows / column; diagonal of P when P is diagonal in all problems
   std::vector<uint32_t> h_slA, h_slT; std::vector<real> h_pdiag; std::vector<unsigned char> h_pdiag_has;
+  // direct KKT solver (cosmo_hip_batch_set_direct): the switch, the requested ordering (empty: default) and the plan built by set_params
+  bool direct_on = false; std::vector<int64_t> direct_perm; BLdlPlan* ldl = nullptr;
 };
 
 static int32_t bfail(cosmo_hip_batch* b, int32_t code, const char* fmt, ...) {
@@ -2255,6 +2290,7 @@ extern "C" int32_t cosmo_hip_batch_destroy(cosmo_hip_batch* b) {
   (void)hipSetDevice(b->device);
   if (b->stream) (void)hipStreamSynchronize(b->stream);
   for (void* p : b->allocs) (void)hipFree(p);
+  bldl_free(b->ldl);
   if (b->h_state) (void)hipHostFree(b->h_state);
   if (b->stream) (void)hipStreamDestroy(b->stream);
   delete b;
@@ -2406,6 +2442,10 @@ struct BKernel { const void* fn; int bs; bool image; };
 static BKernel batch_kernel_of(const cosmo_hip_batch* b) {
   bool psd = b->ext_cones;                               // the instantiations with the cones beyond Zero / Nonnegatives / Box / SecondOrderCone
   if (b->force_ext) psd = true;                           // COSMO_HIP_BATCH_EXT=1 (lab switch: that code is a run-time no-op without such cones)
+  if (b->ldl) {                                           // direct KKT solver: the streaming form only (the accelerated loop carries the PSD code, as below)
+    if (b->aa_on) return {(const void*)k_batch_admm_direct<true, true>, COSMO_BS, false};
+    return {psd ? (const void*)k_batch_admm_direct<true, false> : (const void*)k_batch_admm_direct<false, false>, COSMO_BS, false};
+  }
   const bool img = b->d_img != nullptr;
 #if !REAL_IS_FLOAT
   if (img && b->reg_mode == 1 && b->D.sliced) {
@@ -2891,7 +2931,10 @@ extern "C" int32_t cosmo_hip_batch_set_params(cosmo_hip_batch* b, const cosmo_hi
   if (hipSetDevice(b->device) != hipSuccess) return bfail(b, COSMO_HIP_ERR_HIP, "hipSetDevice failed");
   if (!b->have_cones) return bfail(b, COSMO_HIP_ERR_INVALID, "batch_set_cones first");
   for (int k = 0; k < b->nprob; ++k) if (!b->have[k]) return bfail(b, COSMO_HIP_ERR_INVALID, "problem %d not set", k);
-  if (p->kkt_kind != COSMO_HIP_KKT_CG) return bfail(b, COSMO_HIP_ERR_UNSUPPORTED, "batch mode implements the CG KKT solver");
+  const bool direct = b->direct_on && p->kkt_kind == COSMO_HIP_KKT_DIRECT;
+  if (p->kkt_kind != COSMO_HIP_KKT_CG && !direct)
+    return bfail(b, COSMO_HIP_ERR_UNSUPPORTED, b->direct_on ? "batch mode implements the CG and the direct (DIRECT) KKT solvers"
+                                                            : "batch mode implements the CG KKT solver (the direct one after cosmo_hip_batch_set_direct)");
   if (p->adaptive_rho && p->adaptive_rho_interval == 0) return bfail(b, COSMO_HIP_ERR_UNSUPPORTED, "adaptive_rho_interval == 0");
   if (b->finalized) return bfail(b, COSMO_HIP_ERR_INVALID, "batch already finalised");
   b->prm = *p;
@@ -2909,7 +2952,11 @@ extern "C" int32_t cosmo_hip_batch_set_params(cosmo_hip_batch* b, const cosmo_hi
     if (ty >= COSMO_HIP_EXP && ty <= COSMO_HIP_DUAL_POW) b->ext_cones = true;
     if ((ty == COSMO_HIP_PSD_SQUARE || ty == COSMO_HIP_PSD_TRIANGLE) && b->cones.dim[c] > 1) b->ext_cones = true;
   }
-  if ((rc = build_lds_images(b))) return rc;               // needs the host CSR copies that bmat_upload releases
+  if (direct) {                                            // union analysis + refill maps (needs the host CSR copies that bmat_upload releases); no LDS image
+    b->d_img = nullptr; b->reg_mode = 0; D.regcg = 0;
+    const int32_t drc = bldl_build(nprob, n, m, b->hPT, b->hA, b->direct_perm, &b->ldl, &D.ldl, b->err);
+    if (drc) { bldl_free(b->ldl); b->ldl = nullptr; return drc; }
+  } else if ((rc = build_lds_images(b))) return rc;        // needs the host CSR copies that bmat_upload releases
   if (b->d_img && (b->reg_mode == 1 || (b->reg_mode == 0 && D.regcg)) && !b->h_permA.empty()) {        // (no image: the streaming kernel runs and needs none of this)
     if ((rc = bup(b, &D.permA, b->h_permA))) return rc;
     if ((rc = bup(b, &D.permT, b->h_permT))) return rc;
@@ -3033,6 +3080,10 @@ extern "C" int32_t cosmo_hip_batch_set_params(cosmo_hip_batch* b, const cosmo_hi
   for (long long k = 0; k < tl; ++k) tt[k] = p->tol_constant / pow((real)(k + 1), p->tol_exponent);
   if ((rc = bup(b, &D.tol_table, tt))) return rc;
   D.tol_len = tl;
+  if (b->ldl) {                                            // the first factorisation of every member and the inertia check (kktsolver.jl:304)
+    if ((rc = bldl_setup_factor(b->ldl, D.ldl, b->stream, nprob, (int)n, (int)m, (real)p->sigma, D.PT.rowptr, D.PT.val, D.PT.nz_off, D.A.rowptr, D.A.val,
+                                D.A.nz_off, D.rho, b->err))) return rc;
+  }
   b->finalized = true;
   b->hq.clear(); b->hq.shrink_to_fit();
   return COSMO_HIP_OK;
@@ -3197,6 +3248,10 @@ extern "C" int32_t cosmo_hip_batch_optimize(cosmo_hip_batch* b, cosmo_hip_result
       break;
     }
   }
+  if (b->ldl) {                                            // a zero / non-finite pivot after a rho update ends the call as it ends a single handle's optimize
+    const int bad = bldl_first_failed(b->ldl, b->D.ldl, b->stream, b->nprob);
+    if (bad >= 0) return bfail(b, COSMO_HIP_ERR_INVALID, "direct KKT solver: zero or non-finite pivot in the LDL' factorisation (member %d)", bad);
+  }
   const double el = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
   for (int k = 0; k < b->nprob; ++k) {
     cosmo_hip_result& r = results[k];
@@ -3217,7 +3272,7 @@ extern "C" int32_t cosmo_hip_batch_optimize(cosmo_hip_batch* b, cosmo_hip_result
 // iterates as a one-problem streaming batch; certificates and time limit as there.  Requirements (batch_multi_supported): one problem, no accelerator,
 // no PSD cone of side 17..64 (their Jacobi workspace is sized per launch).  All batches carry the group's parameters.
 // ---------------------------------------------------------------------------------------------------------------------
-bool batch_multi_supported(const cosmo_hip_batch* b) { return b && b->finalized && b->nprob == 1 && !b->aa_on && b->D.nmid == 0 && b->D.A.rowptr != nullptr; }
+bool batch_multi_supported(const cosmo_hip_batch* b) { return b && b->finalized && b->nprob == 1 && !b->aa_on && !b->ldl && b->D.nmid == 0 && b->D.A.rowptr != nullptr; }
 bool batch_multi_needs_ext(const cosmo_hip_batch* b) { return b->D.npsd > 0 || b->D.n3 > 0; }
 
 int32_t batch_multi_optimize(cosmo_hip_batch** bs, int count, bool ext, cosmo_hip_result* results) {
@@ -3331,4 +3386,28 @@ extern "C" int32_t cosmo_hip_batch_get_iterates(cosmo_hip_batch* b, int64_t k, r
   if (s) BHIP(b, hipMemcpy(s, b->D.s + (size_t)k * m, m * sizeof(real), hipMemcpyDeviceToHost));
   if (mu) BHIP(b, hipMemcpy(mu, b->D.mu + (size_t)k * m, m * sizeof(real), hipMemcpyDeviceToHost));
   return COSMO_HIP_OK;
+}
+
+// ---- direct KKT solver in batch mode (batch_ldl.h / batch_ldl.hip) ----------------------------------------------------------------------------
+extern "C" int32_t cosmo_hip_batch_set_direct(cosmo_hip_batch* b, int32_t on, const int64_t* perm) {
+  if (!b) return COSMO_HIP_ERR_INVALID;
+  if (b->finalized) return bfail(b, COSMO_HIP_ERR_INVALID, "batch_set_direct: call before batch_set_params (the kernel form is chosen there)");
+  b->direct_on = on != 0;
+  b->direct_perm.clear();
+  if (b->direct_on && perm) b->direct_perm.assign(perm, perm + (b->n + b->m));
+  return COSMO_HIP_OK;
+}
+
+extern "C" int32_t cosmo_hip_batch_direct_info(cosmo_hip_batch* b, int64_t out[8]) {
+  if (!b || !out) return COSMO_HIP_ERR_INVALID;
+  if (!b->ldl) return bfail(b, COSMO_HIP_ERR_INVALID, "batch_direct_info: the batch has no direct KKT solver (batch_set_direct, then set_params with kkt_kind DIRECT)");
+  if (hipSetDevice(b->device) != hipSuccess) return bfail(b, COSMO_HIP_ERR_HIP, "hipSetDevice failed");
+  return bldl_info(b->ldl, b->D.ldl, b->stream, b->nprob, out, b->err);
+}
+
+extern "C" int32_t cosmo_hip_batch_direct_counts(cosmo_hip_batch* b, int64_t* out) {
+  if (!b || !out) return COSMO_HIP_ERR_INVALID;
+  if (!b->ldl) return bfail(b, COSMO_HIP_ERR_INVALID, "batch_direct_counts: the batch has no direct KKT solver (batch_set_direct, then set_params with kkt_kind DIRECT)");
+  if (hipSetDevice(b->device) != hipSuccess) return bfail(b, COSMO_HIP_ERR_HIP, "hipSetDevice failed");
+  return bldl_counts(b->ldl, b->D.ldl, b->stream, b->nprob, out, b->err);
 }

@@ -55,6 +55,7 @@ struct cosmo_hip_batch_group {
   std::vector<GProblem> prob;
   std::vector<GClass> cls;
   bool finalized = false, aa_on = false;
+  bool direct_on = false;         // cosmo_hip_batch_group_set_direct: every class's batch takes kkt_kind DIRECT (cosmo_hip_batch_set_direct)
   int last_workers = 0; long long last_jobs = 0, last_merged = 0;     // of the last optimize: worker threads, jobs (merged sets + batch classes + members on their own handles), classes in merged sets
   cosmo_hip_accel_params aa;
   cosmo_hip_params prm;
@@ -159,6 +160,15 @@ extern "C" int32_t cosmo_hip_batch_group_set_accelerator(cosmo_hip_batch_group* 
   return COSMO_HIP_OK;
 }
 
+// the direct KKT solver in every class's batch (cosmo_hip_batch_set_direct with the default ordering); before set_params.  Classes the batch kernels
+// still refuse keep their own handles.
+extern "C" int32_t cosmo_hip_batch_group_set_direct(cosmo_hip_batch_group* g, int32_t on) {
+  if (!g) return COSMO_HIP_ERR_INVALID;
+  if (g->finalized) return gfail(g, COSMO_HIP_ERR_INVALID, "batch_group_set_direct: after set_params");
+  g->direct_on = on != 0;
+  return COSMO_HIP_OK;
+}
+
 // Partitions the problems into classes of identical structure and finalises one cosmo_hip_batch per class -- or, where the batch kernels refuse the
 // structure (COSMO_HIP_ERR_UNSUPPORTED), one single-problem handle per member.  Any other error of a class's set-up, and a member that no path of the
 // library takes, is the group's error with the offending problem named; the group then holds no classes and set_params may be called again.
@@ -205,6 +215,7 @@ extern "C" int32_t cosmo_hip_batch_group_set_params(cosmo_hip_batch_group* g, co
     }
     rc = cosmo_hip_batch_set_cones_ex(C.b, (int64_t)p0.ctype.size(), p0.ctype.data(), p0.cdim.data(), bl.data(), bu.data(), p0.cparam.data());
     if (rc == COSMO_HIP_OK && g->aa_on) rc = cosmo_hip_batch_set_accelerator(C.b, &g->aa);
+    if (rc == COSMO_HIP_OK && g->direct_on) rc = cosmo_hip_batch_set_direct(C.b, 1, nullptr);
     if (rc == COSMO_HIP_OK) rc = cosmo_hip_batch_set_params(C.b, prm);
     if (rc == COSMO_HIP_ERR_UNSUPPORTED) {
       // not a structure of the persistent kernels: one single-problem handle per member instead

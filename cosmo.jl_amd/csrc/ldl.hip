@@ -22,6 +22,7 @@
 // registers yet.  Together with the single workgroup of a wide supernode this is why BASELINE config 5 factorises slowly.
 #include "device_utils.h"
 #include "ldl.h"
+#include "ldl_dev.h"
 #include <chrono>
 #include <math.h>
 
@@ -115,69 +116,15 @@ __global__ __launch_bounds__(LDL_BS) void k_ldl_refill(const Ctl* __restrict__ c
   }
 }
 
-// row position of permuted row `row` in rows_J (the columns of J come first, the rest is ascending)
-__device__ __forceinline__ int ldl_rowpos(const int* __restrict__ rows, int w, int nr, long long f, int row) {
-  if (row < f + w) return (int)(row - f);
-  int lo = w, hi = nr - 1;
-  while (lo < hi) { const int mid = (lo + hi) >> 1; if (rows[mid] < row) lo = mid + 1; else hi = mid; }
-  return lo;
-}
-
 __global__ __launch_bounds__(LDL_BS) void k_ldl_factor(Ctl* __restrict__ ctl, int cond, const int* __restrict__ lvl, const int* __restrict__ sn_first,
                                                        const long long* __restrict__ sn_rp, const int* __restrict__ sn_rows,
                                                        const long long* __restrict__ sn_poff, const int* __restrict__ desc_ptr,
                                                        const int* __restrict__ desc, real* __restrict__ Lx, int* __restrict__ dstat) {
   if (ldl_skip(ctl, cond)) return;
-  const int tid = threadIdx.x;
-  const int J = lvl[blockIdx.x];
-  const long long f = sn_first[J];
-  const int w = sn_first[J + 1] - (int)f;
-  const int nr = (int)(sn_rp[J + 1] - sn_rp[J]);
-  const int* rows = sn_rows + sn_rp[J];
-  real* X = Lx + sn_poff[J];
-  // 1. updates from the descendants, ascending
-  for (int d = desc_ptr[J]; d < desc_ptr[J + 1]; ++d) {
-    const int K = desc[3 * d], r0 = desc[3 * d + 1], r1 = desc[3 * d + 2];
-    const int wk = sn_first[K + 1] - sn_first[K];
-    const int nk = (int)(sn_rp[K + 1] - sn_rp[K]);
-    const int* rk = sn_rows + sn_rp[K];
-    const real* XK = Lx + sn_poff[K];
-    const int na = nk - r0, nb = r1 - r0;
-    for (long long t = tid; t < (long long)na * nb; t += LDL_BS) {
-      const int b = (int)(t / na), a = (int)(t % na);
-      if (a < b) continue;
-      real s = R(0.0);
-      for (int c = 0; c < wk; ++c) {
-        const real* col = XK + (long long)c * nk;
-        s += col[r0 + a] * (col[c] * col[r0 + b]);
-      }
-      const int ra = (a < nb) ? rk[r0 + a] - (int)f : ldl_rowpos(rows, w, nr, f, rk[r0 + a]);
-      const int cb = rk[r0 + b] - (int)f;
-      X[ra + (long long)cb * nr] -= s;
-    }
-    __syncthreads();
-  }
-  // 2. dense LDL' of the diagonal block, panel scaled column by column
   int pos = 0;
   bool bad = false;
-  for (int c = 0; c < w; ++c) {
-    const real* colc = X + (long long)c * nr;
-    const real d = colc[c];
-    const int nrr = nr - c - 1, ncc = w - c - 1;
-    for (long long t = tid; t < (long long)nrr * ncc; t += LDL_BS) {
-      const int c2 = c + 1 + (int)(t / nrr), r = c + 1 + (int)(t % nrr);
-      if (r < c2) continue;
-      X[r + (long long)c2 * nr] -= colc[r] * (colc[c2] / d);
-    }
-    __syncthreads();
-    for (int r = c + 1 + tid; r < nr; r += LDL_BS) X[r + (long long)c * nr] = colc[r] / d;
-    if (tid == 0) {
-      if (!(d != R(0.0) && isfinite(d))) bad = true;
-      if (d > R(0.0)) pos += 1;
-    }
-    __syncthreads();
-  }
-  if (tid == 0) {
+  ldl_factor_sn<LDL_BS>(lvl[blockIdx.x], sn_first, sn_rp, sn_rows, sn_poff, desc_ptr, desc, Lx, pos, bad);
+  if (threadIdx.x == 0) {
     if (pos) atomicAdd(&dstat[1], pos);               // integer count of positive pivots (inertia check)
     if (bad) {
       dstat[0] = 1;
@@ -201,30 +148,7 @@ __global__ __launch_bounds__(LDL_BS) void k_ldl_fwd(const Ctl* __restrict__ ctl,
                                                     const long long* __restrict__ sn_poff, const int* __restrict__ desc_ptr,
                                                     const int* __restrict__ desc, const real* __restrict__ Lx, real* __restrict__ y) {
   if (guard && ctl->halt) return;
-  const int tid = threadIdx.x;
-  const int J = lvl[blockIdx.x];
-  const int f = sn_first[J];
-  const int w = sn_first[J + 1] - f;
-  const int nr = (int)(sn_rp[J + 1] - sn_rp[J]);
-  const real* X = Lx + sn_poff[J];
-  for (int d = desc_ptr[J]; d < desc_ptr[J + 1]; ++d) {
-    const int K = desc[3 * d], r0 = desc[3 * d + 1], r1 = desc[3 * d + 2];
-    const int fk = sn_first[K], wk = sn_first[K + 1] - fk;
-    const int nk = (int)(sn_rp[K + 1] - sn_rp[K]);
-    const int* rk = sn_rows + sn_rp[K];
-    const real* XK = Lx + sn_poff[K];
-    for (int b = r0 + tid; b < r1; b += LDL_BS) {
-      real s = R(0.0);
-      for (int c = 0; c < wk; ++c) s += XK[b + (long long)c * nk] * y[fk + c];
-      y[rk[b]] -= s;
-    }
-    __syncthreads();
-  }
-  for (int c = 0; c + 1 < w; ++c) {
-    const real yc = y[f + c];
-    for (int r = c + 1 + tid; r < w; r += LDL_BS) y[f + r] -= X[r + (long long)c * nr] * yc;
-    __syncthreads();
-  }
+  ldl_fwd_sn<LDL_BS>(lvl[blockIdx.x], sn_first, sn_rp, sn_rows, sn_poff, desc_ptr, desc, Lx, y);
 }
 
 // backward solve L' x = D^-1 y for the supernodes of one level (ancestors already solved)
@@ -232,27 +156,7 @@ __global__ __launch_bounds__(LDL_BS) void k_ldl_bwd(const Ctl* __restrict__ ctl,
                                                     const long long* __restrict__ sn_rp, const int* __restrict__ sn_rows,
                                                     const long long* __restrict__ sn_poff, const real* __restrict__ Lx, real* __restrict__ y) {
   if (guard && ctl->halt) return;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int J = lvl[blockIdx.x];
-  const int f = sn_first[J];
-  const int w = sn_first[J + 1] - f;
-  const int nr = (int)(sn_rp[J + 1] - sn_rp[J]);
-  const int* rows = sn_rows + sn_rp[J];
-  const real* X = Lx + sn_poff[J];
-  // one wave per column: the rows below the diagonal block (fixed reduction tree)
-  for (int c = wave; c < w; c += LDL_BS / 64) {
-    const real* col = X + (long long)c * nr;
-    real s = R(0.0);
-    for (int r = w + lane; r < nr; r += 64) s += col[r] * y[rows[r]];
-    s = wave_sum(s);
-    if (lane == 0) y[f + c] = y[f + c] / col[c] - s;
-  }
-  __syncthreads();
-  for (int r = w - 1; r > 0; --r) {
-    const real xr = y[f + r];
-    for (int c = tid; c < r; c += LDL_BS) y[f + c] -= X[r + (long long)c * nr] * xr;
-    __syncthreads();
-  }
+  ldl_bwd_sn<LDL_BS>(lvl[blockIdx.x], sn_first, sn_rp, sn_rows, sn_poff, Lx, y);
 }
 
 __global__ __launch_bounds__(LDL_BS) void k_ldl_unperm(Ctl* __restrict__ ctl, int guard, long long N, const int* __restrict__ perm,

@@ -422,7 +422,29 @@ end
 # Per problem the unchanged reference code does the scaling / classification (setup!, src/setup.jl:18-42) and the epilogue
 # (src/solver.jl:167-201); the loop of src/solver.jl:137-176 runs on the device for all problems at once.
 # ---------------------------------------------------------------------------------------------------------------------
-function optimize_hip_batch!(models::Vector{COSMO.Workspace{T}}; device::Integer = 0, kkt_kind::Int32 = KKT_CG, tol_constant = 1.0, tol_exponent = 1.5) where {T <: HipFloat}
+# The direct KKT solver in batch mode (csrc/batch_ldl.hip) on a raw cosmo_hip_batch* `b` of library T: the switch (before set_params; perm = nothing: the
+# default ordering, else n + m 0-based entries), the figures of the batch's factor and the factorisations of every member.
+function batch_set_direct!(::Type{T}, b::Ptr{Cvoid}, on::Bool, perm::Union{Vector{Int64}, Nothing} = nothing) where {T <: HipFloat}
+    GC.@preserve perm ccall((:cosmo_hip_batch_set_direct, libpath(T)), Int32, (Ptr{Cvoid}, Int32, Ptr{Int64}), b, Int32(on), perm === nothing ? C_NULL : pointer(perm))
+end
+function batch_direct_info(::Type{T}, b::Ptr{Cvoid}) where {T <: HipFloat}
+    out = zeros(Int64, 8)
+    rc = ccall((:cosmo_hip_batch_direct_info, libpath(T)), Int32, (Ptr{Cvoid}, Ptr{Int64}), b, out)
+    rc == 0 || error("cosmo_hip_batch_direct_info failed (code $rc)")
+    return (nnz_L = out[1], panel_size = out[2], supernodes = out[3], height = out[4], max_width = out[5], analysis_ns = out[6], factorizations = out[7],
+            min_positive_pivots = out[8])
+end
+function batch_direct_counts(::Type{T}, b::Ptr{Cvoid}, nprob::Integer) where {T <: HipFloat}
+    out = zeros(Int64, nprob)
+    rc = ccall((:cosmo_hip_batch_direct_counts, libpath(T)), Int32, (Ptr{Cvoid}, Ptr{Int64}), b, out)
+    rc == 0 || error("cosmo_hip_batch_direct_counts failed (code $rc)")
+    return out
+end
+
+# direct_batch = true (with kkt_kind = KKT_DIRECT): every structure class runs the direct KKT solver inside its persistent batch kernel
+# (cosmo_hip_batch_group_set_direct) instead of one single-problem handle per member
+function optimize_hip_batch!(models::Vector{COSMO.Workspace{T}}; device::Integer = 0, kkt_kind::Int32 = KKT_CG, tol_constant = 1.0, tol_exponent = 1.5,
+                             direct_batch::Bool = false) where {T <: HipFloat}
     isempty(models) && return COSMO.Result{T}[]
     LIBT = libpath(T)
     settings = models[1].settings
@@ -472,6 +494,7 @@ function optimize_hip_batch!(models::Vector{COSMO.Workspace{T}}; device::Integer
         end
         ap = accel_params_from(settings)                     # _make_accelerator! (src/setup.jl:10-16) for every problem; before set_params
         ap === nothing || gcheck(ccall((:cosmo_hip_batch_group_set_accelerator, LIBT), Int32, (Ptr{Cvoid}, Ref{AccelParams}), g, Ref(ap)))
+        direct_batch && gcheck(ccall((:cosmo_hip_batch_group_set_direct, LIBT), Int32, (Ptr{Cvoid}, Int32), g, Int32(1)))
         # ws.times.setup_time of this call's set-up phase (solver.jl:246: what the automatic rho interval of the members that run on their own handles is measured against)
         prm = Ref(params_from(settings, kkt_kind; tol_constant = tol_constant, tol_exponent = tol_exponent, setup_time = time() - t_start))
         gcheck(ccall((:cosmo_hip_batch_group_set_params, LIBT), Int32, (Ptr{Cvoid}, Ref{Params}), g, prm))   # classes + classify_constraints! + set_rho_vec! per problem

@@ -120,6 +120,12 @@ class Settings:
     # distributed run, no chordal decomposition to apply, a structure the batch kernels take, an image small enough for the CU's LDS) -- same statuses and
     # solutions to solver accuracy, not the same bits; the model then has no single-problem handle (model.handle stays None).
     persistent_kernel: bool = False
+    # QdldlKKTSolver in batch mode (not a field of COSMO.Settings): optimize_batch otherwise gives every member of a batch with that solver its own
+    # single-problem handle (its own symbolic analysis, its own chain of launches per iteration).  True: the batch kernels solve the KKT systems by
+    # LDL' themselves (csrc/batch_ldl.hip): one analysis of the union of the members' patterns (with_options(QdldlKKTSolver, perm=...) is honoured),
+    # one factor per member in its persistent workgroup, refactorised there when its rho changes -- same statuses and solutions to solver accuracy as
+    # the single handle, not the same bits.  With persistent_kernel=True it also routes optimize() of one small model to that form.
+    direct_batch: bool = False
     # accepted for drop-in compatibility with COSMO.Settings (src/settings.jl:101-139); they do not touch the hot path:
     nearly_ratio: float = 100.0            # only read by the MOI wrapper (is_primal_nearly_feasible, src/MOI_wrapper.jl:558,587)
     adaptive_rho_fraction: float = 0.4     # only with adaptive_rho_interval = 0 (the automatic interval, solver.jl:244-256)
@@ -874,6 +880,9 @@ def prepare_batch(models: Sequence[Model], device: int):
             raise ValueError("optimize_batch: all problems of a batch share ONE Settings object (per-problem settings are not supported)")
     B = _ffi.Batch(len(models), n, m, device, dtype=getattr(models[0], "dtype", np.float64))
     _install_accelerator(B, st)                           # before set_params: the accelerated loop runs inside the persistent kernels (csrc/batch.hip)
+    direct, perm = _direct_batch_of(st)
+    if direct:
+        B.set_direct(True, perm)                          # before set_params: the LDL' form of the batch kernels (csrc/batch_ldl.hip)
     bl, bu = [], []
     for k, md in enumerate(models):                      # setup! per problem (scaling on the host, as in the reference)
         if st.scaling != 0 and not md.is_scaled:
@@ -890,6 +899,16 @@ def prepare_batch(models: Sequence[Model], device: int):
     B.set_iterates(np.concatenate([md.x for md in models]), np.concatenate([md.s for md in models]),
                    np.concatenate([md.mu for md in models]))
     return B, st
+
+
+def _direct_batch_of(st: Settings):
+    """(Settings.direct_batch applies, the ordering of with_options(QdldlKKTSolver, perm=...) or None)"""
+    kkt, kw = st.kkt_solver, {}
+    if isinstance(kkt, OptionsFactory):
+        kkt, kw = kkt.solver, kkt.kwargs
+    if not (st.direct_batch and kkt == QdldlKKTSolver):
+        return False, None
+    return True, kw.get("perm")
 
 
 def _structure_key(md: Model):
@@ -923,10 +942,12 @@ def _check_batch_psd_projection(models) -> None:
 
 
 def _batch_kernels_take(md: Model) -> bool:
-    """What cosmo_hip_batch_* accepts (csrc/batch.hip): CG solver kinds, the cone types of batch mode with PSD cones of side <= 64, a fixed rho interval."""
+    """What cosmo_hip_batch_* accepts (csrc/batch.hip): CG solver kinds (and QdldlKKTSolver with Settings.direct_batch), the cone types of batch mode with
+    PSD cones of side <= 64, a fixed rho interval."""
     st = md.settings
     kkt = st.kkt_solver.solver if isinstance(st.kkt_solver, OptionsFactory) else st.kkt_solver
-    if kkt not in (CGIndirectKKTSolver, CGSingleReductionKKTSolver, CGJacobiKKTSolver) or (st.adaptive_rho and st.adaptive_rho_interval == 0):
+    kinds = (CGIndirectKKTSolver, CGSingleReductionKKTSolver, CGJacobiKKTSolver) + ((QdldlKKTSolver,) if st.direct_batch else ())
+    if kkt not in kinds or (st.adaptive_rho and st.adaptive_rho_interval == 0):
         return False
     acc = st.accelerator.solver if isinstance(st.accelerator, OptionsFactory) else st.accelerator
     if isinstance(acc, type) and issubclass(acc, AndersonAccelerator) and acc.accel_kind != _ffi.ACCEL_ANDERSON:
@@ -954,6 +975,8 @@ def prepare_batch_group(models: Sequence[Model], device: int):
             raise ValueError("optimize_batch: all problems of a batch share ONE Settings object (per-problem settings are not supported)")
     G = _ffi.BatchGroup(len(models), device, dtype=getattr(models[0], "dtype", np.float64))
     _install_accelerator(G, st)
+    if _direct_batch_of(st)[0]:
+        G.set_direct(True)                                # every class's batch takes the LDL' form (default ordering: the classes differ in size)
     for k, md in enumerate(models):
         n, m = md.n, md.m
         if st.scaling != 0 and not md.is_scaled:
@@ -998,6 +1021,9 @@ def _solve_shard_on_device(models: Sequence[Model], device: int) -> List[Result]
     if mixed:
         LAST_BATCH_INFO.update(B.run_info())                       # worker threads / jobs of the group's bounded pool, structure classes
         LAST_BATCH_INFO["own_handle_members"] = int(np.sum(B.class_info(with_modes=True)[2] == 1))     # members the batch kernels refused
+    elif _direct_batch_of(st)[0]:
+        LAST_BATCH_INFO["direct_info"] = B.direct_info()               # the LDL' form of the batch kernels ran (csrc/batch_ldl.hip)
+        LAST_BATCH_INFO["direct_counts"] = B.direct_counts()
     out = []
     for k, (md, r) in enumerate(zip(models, rs)):
         w, w_prev, s, mu = B.get_iterates(k)

@@ -518,6 +518,18 @@ COSMO_HIP_API int32_t cosmo_hip_batch_get_counters(cosmo_hip_batch* b, int64_t* 
  * (ABI 1004: out grew from 4 to 8 entries) */
 COSMO_HIP_API int32_t cosmo_hip_batch_kernel_info(cosmo_hip_batch* b, int64_t out[8]);
 COSMO_HIP_API int32_t cosmo_hip_batch_get_iterates(cosmo_hip_batch* b, int64_t k, cosmo_hip_real* w, cosmo_hip_real* w_prev, cosmo_hip_real* s, cosmo_hip_real* mu);
+/* Direct KKT solver in batch mode (csrc/batch_ldl.hip): on = 1 lets the next cosmo_hip_batch_set_params take kkt_kind COSMO_HIP_KKT_DIRECT (without it
+ * set_params returns UNSUPPORTED for that kind).  One symbolic analysis of the union of the members' K patterns; perm: NULL = the default ordering, else
+ * n + m entries in the convention of cosmo_hip_ldl_analyze.  Every problem is factorised and solved by its own persistent workgroup and refactorised
+ * there when its rho changes.  set_params then returns UNSUPPORTED when the panels of all members exceed the storage budget (half of the free device
+ * memory), and INVALID with "Objective function is not convex. (member k)" when a member's first factorisation has not exactly n positive pivots.
+ * A zero or non-finite pivot later in the loop stops that member; cosmo_hip_batch_optimize then returns INVALID naming it.  Call before set_params. */
+COSMO_HIP_API int32_t cosmo_hip_batch_set_direct(cosmo_hip_batch* b, int32_t on, const int64_t* perm /* NULL or n + m */);
+/* out = {nnz(L), panel values per problem, supernodes, tree height, widest supernode, analysis time in ns, factorisations of all members together,
+ * smallest positive-pivot count of the members' last factorisations} */
+COSMO_HIP_API int32_t cosmo_hip_batch_direct_info(cosmo_hip_batch* b, int64_t out[8]);
+/* factorisations of every member so far (the set-up one included): out[nprob] */
+COSMO_HIP_API int32_t cosmo_hip_batch_direct_counts(cosmo_hip_batch* b, int64_t* out /* nprob */);
 
 /* ---- batches of problems of DIFFERENT structure (csrc/batch_group.hip) ------------------------------------------------------------------
  * The reference's batch is a loop over arbitrary models (src/solver.jl:78).  A group takes every problem with ITS OWN (n, m, cones), partitions
@@ -544,6 +556,8 @@ COSMO_HIP_API int32_t cosmo_hip_batch_group_set_scaling(cosmo_hip_batch_group* g
 COSMO_HIP_API int32_t cosmo_hip_batch_group_set_scaling_full(cosmo_hip_batch_group* g, int64_t k, const cosmo_hip_real* D, const cosmo_hip_real* Dinv, const cosmo_hip_real* E,
                                                const cosmo_hip_real* Einv, double c, double cinv);
 COSMO_HIP_API int32_t cosmo_hip_batch_group_set_accelerator(cosmo_hip_batch_group* g, const cosmo_hip_accel_params* p);
+/* cosmo_hip_batch_set_direct(on, default ordering) for every class's batch; before set_params.  Classes the batch kernels still refuse keep their own handles */
+COSMO_HIP_API int32_t cosmo_hip_batch_group_set_direct(cosmo_hip_batch_group* g, int32_t on);
 COSMO_HIP_API int32_t cosmo_hip_batch_group_set_params(cosmo_hip_batch_group* g, const cosmo_hip_params* p);
 /* number of structure classes; class_of[k] and mode_of[k] for every problem (nprob entries each, may be NULL): mode 0 = the class runs on a
  * persistent batch kernel, 1 = its structure is outside the batch kernels (PSD side > 64, a MINRES solver kind, ...) and every member is solved
