@@ -332,7 +332,6 @@ inline AaState* aa_of(cosmo_hip_handle* h) { return static_cast<AaState*>(h->acc
 
 }  // namespace
 
-int32_t comm_allreduce_sum(cosmo_hip_handle* h, real* buf, size_t count);      // comm.hip
 // row-sharded runs: the partial array(s) starting at `p` summed over the ranks, slot by slot (same count on every rank; entries beyond a
 // rank's grid are zero from the allocation on)
 static int32_t aa_share(cosmo_hip_handle* h, AaState* S, real* p) {

@@ -9,26 +9,6 @@
 #include "internal.h"
 #include "device_utils.h"
 
-// launchers defined in kernels.hip
-int32_t launch_project_simple_inplace(cosmo_hip_handle* h, real* s);
-int32_t launch_z(cosmo_hip_handle* h, int guard);
-int32_t launch_soc(cosmo_hip_handle* h, real* s, int guard);
-int32_t launch_set_w(cosmo_hip_handle* h, const real* x0, const real* s0, const real* mu0);
-int32_t launch_recover_mu(cosmo_hip_handle* h);
-int32_t launch_rho_from_classes(cosmo_hip_handle* h, real rho0);
-int32_t enqueue_cg_iterations(cosmo_hip_handle* h, int guard, int k_begin, int count);
-int32_t enqueue_cg_start(cosmo_hip_handle* h, int guard, real tol_k);
-int32_t enqueue_rhs(cosmo_hip_handle* h, int guard);
-int32_t enqueue_y2_only(cosmo_hip_handle* h);
-int32_t enqueue_tail(cosmo_hip_handle* h, int loop_mode);
-int32_t enqueue_count_solve(cosmo_hip_handle* h);
-int32_t enqueue_clear_stall(cosmo_hip_handle* h);
-int32_t enqueue_check(cosmo_hip_handle* h, int guard, int mode);
-// minres.hip
-int32_t minres_enqueue_solve(cosmo_hip_handle* h, int guard, bool from_loop);
-int32_t minres_alloc(cosmo_hip_handle* h);
-int32_t minres_resume(cosmo_hip_handle* h, int extra);
-
 // ---------------------------------------------------------------------------------------------------------------------
 int32_t cosmo_fail(cosmo_hip_handle* h, int32_t code, const char* fmt, ...) {
   char buf[1024];
@@ -256,10 +236,7 @@ extern "C" int32_t cosmo_hip_destroy(cosmo_hip_handle* h) {
   (void)hipSetDevice(h->device);
   if (h->stream) (void)hipStreamSynchronize(h->stream);
   free_csr(h->A); free_csr(h->AT); free_csr(h->P); free_csr(h->PT);
-  free_op_split(h);
-  ldl_free(h);
-  pcg_free(h);
-  sr_free(h);
+  kkt_free(h);
   (void)cosmo_hip_comm_destroy(h);
   rs_free(h);
   aa_free(h);
@@ -314,8 +291,7 @@ extern "C" int32_t cosmo_hip_set_problem(cosmo_hip_handle* h, int64_t n, int64_t
     for (int k = At.rowptr[j]; k < At.rowptr[j + 1]; ++k) { PT.col[p] = At.col[k] + (int)n; PT.val[p] = At.val[k]; ++p; }
   }
   PT.rowptr[n] = (int)p;
-  free_op_split(h);
-  ldl_free(h);                       // the factor's analysis belongs to the old pattern
+  kkt_free(h);                       // the reduced operator and the factor's analysis belong to the old pattern
   CHK(upload_csr(h, Am, h->A, (int)n));
   CHK(upload_csr(h, At, h->AT, (int)m));
   CHK(upload_csr(h, Pm, h->P, (int)n));
@@ -335,7 +311,7 @@ extern "C" int32_t cosmo_hip_set_problem(cosmo_hip_handle* h, int64_t n, int64_t
   CHK(h2d(h, h->q, q, (size_t)n));
   CHK(h2d(h, h->b, b, (size_t)m));
   h->has_scaling = false; h->cinv = 1.0;
-  h->have_problem = true; h->have_cones = false; h->have_iterates = false;
+  h->have_problem = true; h->have_cones = false; h->have_params = false; h->have_iterates = false;
   HIPCHK(h, hipMemsetAsync(h->ctl, 0, sizeof(Ctl), h->stream));
   h->host_iter = h->host_solves = 0; h->stalls = 0; h->budget = 12;
   return COSMO_HIP_OK;
@@ -505,12 +481,10 @@ void free_op_split(cosmo_hip_handle* h) {
   h->op_split = false; h->op_nsingle = 0;
 }
 
-// force: build the split for ANY A (row-sharded runs need a reduced operator that does not depend on h->A, which becomes a row slice)
-int32_t build_op_split(cosmo_hip_handle* h, bool force) {
+// any_a: build the split for ANY A (row-sharded runs need a reduced operator that does not depend on h->A, which becomes a row slice).
+// The rho-dependent values are filled by refresh_op_split (kkt_configure, once the route is final).
+int32_t build_op_split(cosmo_hip_handle* h, bool any_a, bool fold, int factor_min) {
   free_op_split(h);
-  if (const char* e = getenv("COSMO_HIP_OP_SPLIT")) if (e[0] == '0' && !force) return COSMO_HIP_OK;
-  // CG always; the reduced MINRES only when a row-sharded handle needs an operator that does not depend on the local slices (force)
-  if (h->prm.kkt_kind != COSMO_HIP_KKT_CG && !(force && h->prm.kkt_kind == COSMO_HIP_KKT_MINRES_REDUCED)) return COSMO_HIP_OK;
   const long long n = h->n, m = h->m, nnzA = h->A.nnz, nnzP = h->P.nnz;
   if (m == 0 || nnzA == 0) return COSMO_HIP_OK;
   std::vector<int> arp((size_t)m + 1), acol((size_t)nnzA), prp((size_t)n + 1), pcol((size_t)std::max<long long>(nnzP, 1));
@@ -520,7 +494,7 @@ int32_t build_op_split(cosmo_hip_handle* h, bool force) {
   if (nnzP) { CHK(d2h(h, pcol.data(), h->P.col, (size_t)nnzP)); CHK(d2h(h, pval.data(), h->P.val, (size_t)nnzP)); }
   long long nsingle = 0;
   for (long long i = 0; i < m; ++i) if (arp[i + 1] - arp[i] == 1) ++nsingle;
-  if (nsingle * 2 < nnzA && !force) return COSMO_HIP_OK;
+  if (nsingle * 2 < nnzA && !any_a) return COSMO_HIP_OK;
   // Am: rows with >= 2 nonzeros, compact
   HostCsr Am, AmT, PTm;
   std::vector<int> mrow;
@@ -570,23 +544,8 @@ int32_t build_op_split(cosmo_hip_handle* h, bool force) {
   h->op_nsingle = nsingle;
   h->op_split = true;
   prp.resize((size_t)n + 1);
-  CHK(fold_build(h, Am, prp, pcol, pval));      // assembled operator where Am' rho Am is sparse enough (cg_fold.hip)
-  return refresh_op_split(h);
-}
-
-// LAB SWITCH (COSMO_HIP_CG_SR_DEFAULT=1; round 6): kkt_kind CG on an ASSEMBLED reduced operator runs the one-launch
-// single-reduction recurrence (cg_sr.hip: k_sr_M) instead of the literal pair.  Measured as a candidate default and REJECTED (BASELINE config 5:
-// 12.42 vs 11.50 us per Krylov iteration -- the 24-byte gathers of {r, w, s} from 32-byte records cost more than the launch they save, every
-// XCD re-fetches the whole table through the fabric at each kernel boundary --, 236.6 vs 244.9 it/s; and at a 1e-10 stopping threshold the
-// recurrence needs +1.2 % Krylov iterations, outside the +-1 per solve the parity tests allow; profiles/r06_cg_one_launch_default.txt).
-int32_t choose_cg_recurrence(cosmo_hip_handle* h) {
-  if (h->prm.kkt_kind != COSMO_HIP_KKT_CG || h->cg_jacobi || h->cg_sr || !h->op_fold) return COSMO_HIP_OK;
-  if (((FoldPlan*)h->fold)->nd > 0) return COSMO_HIP_OK;          // a partially assembled operator belongs to the literal pair
-  const char* e = getenv("COSMO_HIP_CG_SR_DEFAULT");
-  if (!e || atoi(e) == 0) return COSMO_HIP_OK;
-  h->cg_sr = true; h->cg_sr_auto = true;
-  dfree(&h->cg_ru);                      // the {r, u} records of the literal pair
-  return sr_alloc(h);
+  if (fold) CHK(fold_build(h, Am, prp, pcol, pval, factor_min));      // assembled operator where Am' rho Am is sparse enough (cg_fold.hip)
+  return COSMO_HIP_OK;
 }
 
 extern "C" int32_t cosmo_hip_set_params(cosmo_hip_handle* h, const cosmo_hip_params* p, const real* rho_vec) {
@@ -601,10 +560,6 @@ extern "C" int32_t cosmo_hip_set_params(cosmo_hip_handle* h, const cosmo_hip_par
   const bool reclass = (p->cosmo_infty_min_scaling != h->prm.cosmo_infty_min_scaling) || (p->rho_tol != h->prm.rho_tol);
   h->prm = *p;
   h->auto_rho_fixed_at = -1;
-  h->cg_sr = (p->kkt_kind == COSMO_HIP_KKT_CG_SR);
-  h->cg_sr_auto = false;
-  h->cg_jacobi = (p->kkt_kind == COSMO_HIP_KKT_CG_JACOBI);
-  if (h->cg_sr || h->cg_jacobi) h->prm.kkt_kind = COSMO_HIP_KKT_CG;      // the same reduced operator, split, budget and tail; only the Krylov recurrence differs
   if (reclass) {
     std::vector<real> bhost((size_t)h->m);
     CHK(d2h(h, bhost.data(), h->b, (size_t)h->m));
@@ -621,42 +576,15 @@ extern "C" int32_t cosmo_hip_set_params(cosmo_hip_handle* h, const cosmo_hip_par
   h->ctl_host->kkt_iters_total = 0;
   CHK(h2d(h, h->ctl, h->ctl_host, 1));
   h->host_solves = 0;
-  if (h->prm.kkt_kind != COSMO_HIP_KKT_CG && h->prm.kkt_kind != COSMO_HIP_KKT_DIRECT) CHK(minres_alloc(h));
-  CHK(sr_alloc(h));
   // the Krylov warm start (previous_solution) starts at zero (kktsolver_indirect.jl:32)
   HIPCHK(h, hipMemsetAsync(h->x_tl, 0, sizeof(real) * (size_t)std::max<long long>(h->n, 1), h->stream));
   HIPCHK(h, hipMemsetAsync(h->nu, 0, sizeof(real) * (size_t)std::max<long long>(h->m, 1), h->stream));
   h->have_params = true;
-  // fused direction + A product (k_cg_dirA): one launch less per Krylov iteration, bit-identical; COSMO_HIP_CG_FUSE_DIR=0 disables it
-  // (and with it the assembled operator of cg_fold.hip, which gathers the same {r, u} records)
-  dfree(&h->cg_ru);
-  { bool fuse = (h->prm.kkt_kind == COSMO_HIP_KKT_CG) && !h->cg_sr && h->n > 0;
-    if (const char* e = getenv("COSMO_HIP_CG_FUSE_DIR")) fuse = fuse && atoi(e) != 0;
-    if (fuse) CHK(dalloc(h, &h->cg_ru, 2 * (size_t)h->n)); }
-  CHK(build_op_split(h));     // needs the (scaled) matrices and rho: both final from here on
-  CHK(choose_cg_recurrence(h));
-  if (h->prm.kkt_kind == COSMO_HIP_KKT_DIRECT) {
-    // QdldlKKTSolver (kktsolver.jl:285-307): analysis (kept while the pattern and the requested ordering stay), factorisation, inertia check
-    h->pcg_on = false;
-    const int32_t rc = ldl_setup(h, h->kkt_perm);
-    // no usable factor (failed analysis or allocation, zero pivot, wrong inertia): solves, update_rho and optimize refuse until a set_params
-    // succeeds.  The plan's figures stay readable through cosmo_hip_direct_info (positive pivots of the refused factor).
-    if (rc != COSMO_HIP_OK) { h->have_params = false; h->have_iterates = false; }
-    return rc;
-  }
-  ldl_free(h);
-  if (h->cg_jacobi) {
-    // the opt-in Jacobi-preconditioned CG lives on the ASSEMBLED reduced operator (its diagonal is the preconditioner): no silent fallback to the
-    // unpreconditioned recurrence when the operator cannot be assembled (dense A' rho A: BASELINE config 2, where Jacobi makes the count worse anyway)
-    if (!h->op_fold) return cosmo_fail(h, COSMO_HIP_ERR_UNSUPPORTED, "kkt_kind CG_JACOBI needs the assembled reduced operator (csrc/cg_fold.hip: A' rho A too dense here, or COSMO_HIP_OP_FOLD=0 / COSMO_HIP_CG_FUSE_DIR=0)");
-    // drop a persistent-CG state left by an earlier set_params with COSMO_HIP_CG_PERSIST=1: enqueue_solve_in_loop would otherwise run the
-    // unpreconditioned persistent recurrence against the rebuilt operator
-    h->pcg_on = false;
-    if (h->pcg_sync) { (void)hipFree(h->pcg_sync); h->pcg_sync = nullptr; }
-    if (h->pcg_u2) { (void)hipFree(h->pcg_u2); h->pcg_u2 = nullptr; }
-    return COSMO_HIP_OK;
-  }
-  return pcg_setup(h);        // single-launch CG (opt-in)
+  // needs the (scaled) matrices and rho: both final from here on.  No route (failed analysis or allocation, a zero pivot or the wrong inertia of
+  // the direct solver's factor, an operator Jacobi-PCG cannot use): solves, update_rho and optimize refuse until a set_params succeeds
+  const int32_t rc = kkt_configure(h, false);
+  if (rc != COSMO_HIP_OK) { h->have_params = false; h->have_iterates = false; }
+  return rc;
 }
 
 extern "C" int32_t cosmo_hip_update_rho(cosmo_hip_handle* h, const real* rho_vec) {
@@ -665,12 +593,7 @@ extern "C" int32_t cosmo_hip_update_rho(cosmo_hip_handle* h, const real* rho_vec
   if (h->row_shard) return cosmo_fail(h, COSMO_HIP_ERR_UNSUPPORTED, "update_rho: not available on a row-sharded handle");
   if (!h->have_params || !rho_vec) return cosmo_fail(h, COSMO_HIP_ERR_INVALID, "update_rho: not set up");
   CHK(h2d(h, h->rho, rho_vec, (size_t)h->m));
-  if (h->prm.kkt_kind == COSMO_HIP_KKT_DIRECT) {          // update_rho!(::QdldlKKTSolver): new values, refactor (:316-320)
-    const int32_t rc = ldl_refactor_now(h, false);
-    if (rc != COSMO_HIP_OK) { h->have_params = false; h->have_iterates = false; }    // a zero pivot leaves no usable factor
-    return rc;
-  }
-  return refresh_op_split(h);
+  return kkt_update_rho(h);
 }
 
 extern "C" int32_t cosmo_hip_set_kkt_perm(cosmo_hip_handle* h, int64_t len, const int64_t* perm) {
@@ -809,10 +732,6 @@ extern "C" int32_t cosmo_hip_project(cosmo_hip_handle* h, real* s, int64_t* psd_
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
-static real tol_for_solve(const cosmo_hip_handle* h, long long k) {
-  return h->prm.tol_constant / pow((real)k, h->prm.tol_exponent);  // get_tolerance, kktsolver_indirect.jl:168-170
-}
-
 static void adapt_budget(cosmo_hip_handle* h) {
   const int kmax = h->ctl_host->cg_k_max;
   int nb = kmax + 2;
@@ -843,45 +762,7 @@ extern "C" int32_t cosmo_hip_kkt_solve(cosmo_hip_handle* h, real* lhs, const rea
   if (!h->have_params || !lhs || !rhs) return cosmo_fail(h, COSMO_HIP_ERR_INVALID, "kkt_solve: not set up");
   CHK(h2d(h, h->ls_x, rhs, (size_t)h->n));
   CHK(h2d(h, h->ls_s, rhs + h->n, (size_t)h->m));
-  if (h->prm.kkt_kind == COSMO_HIP_KKT_CG) {
-    CHK(enqueue_y2_only(h));
-    CHK(enqueue_cg_start(h, 0, tol_for_solve(h, h->host_solves + 1)));
-    int k = 0, chunk = std::max(h->budget, 4);
-    bool solved = false;
-    if (h->cg_sr) {
-      CHK(sr_enqueue_start(h, 0));
-      for (;;) {
-        CHK(sr_enqueue_iterations(h, 0, k, chunk));
-        CHK(sync_ctl(h));
-        if (h->ctl_host->cg_done) break;
-        k += chunk;
-        chunk = std::min(chunk * 2, 1024);
-      }
-      solved = true;
-    } else if (h->pcg_on) {
-      CHK(pcg_enqueue_solve(h, 0));
-      CHK(sync_ctl(h));
-      if (h->ctl_host->stalled) {           // the start-up rendezvous failed: nothing was modified, continue with the multi-kernel loop
-        h->pcg_on = false; h->pcg_fallbacks += 1;
-        CHK(enqueue_clear_stall(h));
-      } else {
-        solved = true;
-      }
-    }
-    while (!solved) {
-      CHK(enqueue_cg_iterations(h, 0, k, chunk));
-      CHK(sync_ctl(h));
-      if (h->ctl_host->cg_done) break;
-      k += chunk;
-      chunk = std::min(chunk * 2, 1024);
-    }
-    CHK(enqueue_tail(h, 0));
-    CHK(enqueue_count_solve(h));
-  } else if (h->prm.kkt_kind == COSMO_HIP_KKT_DIRECT) {
-    CHK(ldl_enqueue_solve(h, 0, false));          // the full (n+m) system, as solve!(::QdldlKKTSolver) (kktsolver.jl:310-313)
-  } else {
-    CHK(minres_enqueue_solve(h, 0, false));
-  }
+  CHK(kkt_solve_now(h));
   h->host_solves += 1;
   CHK(sync_ctl(h));
   if (kkt_iters_out) *kkt_iters_out = h->ctl_host->cg_k;
@@ -931,7 +812,7 @@ extern "C" int32_t cosmo_hip_set_iterates(cosmo_hip_handle* h, const real* x0, c
 // the feedback off for the handle (COSMO_HIP_BUDGET_FEEDBACK=0 does so from the start).
 static const int FB_LAG = 2;
 static void feedback_reset(cosmo_hip_handle* h) { h->fb_from = h->fb_recorded; }
-static int32_t solve_budget(cosmo_hip_handle* h, int* budget_out) {
+int32_t solve_budget(cosmo_hip_handle* h, int* budget_out) {
   const int R = cosmo_hip_handle::FB_RING;
   bool& used = h->fb_used[(h->host_solves + 1) % R];         // this solve is number host_solves + 1 (ctl->solves counts completed ones)
   used = false;
@@ -960,7 +841,7 @@ static int32_t solve_budget(cosmo_hip_handle* h, int* budget_out) {
   *budget_out = b;
   return COSMO_HIP_OK;
 }
-static int32_t feedback_record(cosmo_hip_handle* h) {
+int32_t feedback_record(cosmo_hip_handle* h) {
   if (h->fb_mode != 1 || !h->fb_k) return COSMO_HIP_OK;
   const int R = cosmo_hip_handle::FB_RING;
   const int slot = (int)(h->fb_recorded % R);
@@ -973,46 +854,7 @@ static int32_t feedback_record(cosmo_hip_handle* h) {
 
 static int32_t enqueue_solve_in_loop(cosmo_hip_handle* h) {
   CHK(enqueue_rhs(h, 1));
-  if (h->prm.kkt_kind == COSMO_HIP_KKT_CG) {
-    CHK(enqueue_cg_start(h, 1, tol_for_solve(h, h->host_solves + 1)));
-    if (h->cg_sr) {
-      CHK(sr_enqueue_start(h, 1));
-      if (h->exact_launches) {
-        CHK(sr_enqueue_iterations(h, 1, 0, 0));
-        for (int k = 0;; ++k) {
-          CHK(sync_ctl(h));
-          if (h->ctl_host->cg_done || h->ctl_host->halt) break;
-          CHK(sr_enqueue_iterations(h, 1, k, 1));
-        }
-      } else {
-        int bud = 0;
-        CHK(solve_budget(h, &bud));
-        CHK(sr_enqueue_iterations(h, 1, 0, bud));
-        h->cg_k_likely = 0x7fffffff;
-      }
-    } else if (h->pcg_on) {
-      CHK(pcg_enqueue_solve(h, 1));        // the whole Krylov loop in one launch (cg_persist.hip)
-    } else if (h->exact_launches) {
-      // measurement mode: one Krylov iteration per host round trip, so that every launch does full work
-      CHK(enqueue_cg_iterations(h, 1, 0, 0));
-      for (int k = 0;; ++k) {
-        CHK(sync_ctl(h));
-        if (h->ctl_host->cg_done || h->ctl_host->halt) break;
-        CHK(enqueue_cg_iterations(h, 1, k, 1));
-      }
-    } else {
-      int bud = 0;
-      CHK(solve_budget(h, &bud));
-      CHK(enqueue_cg_iterations(h, 1, 0, bud));
-      h->cg_k_likely = 0x7fffffff;
-    }
-    CHK(enqueue_tail(h, 1));
-    CHK(feedback_record(h));
-  } else if (h->prm.kkt_kind == COSMO_HIP_KKT_DIRECT) {
-    CHK(ldl_enqueue_solve(h, 1, true));
-  } else {
-    CHK(minres_enqueue_solve(h, 1, true));
-  }
+  CHK(kkt_enqueue_loop_solve(h));
   h->host_solves += 1;
   return COSMO_HIP_OK;
 }
@@ -1057,17 +899,7 @@ static int32_t resolve_stall(cosmo_hip_handle* h) {
     // enqueued behind it were no-ops and say nothing; window-rule ('wide') budgets are not the feedback's stalls
     if (h->fb_mode == 1 && h->fb_used[(h->ctl_host->solves + 1) % cosmo_hip_handle::FB_RING]) { h->fb_stalls += 1; if (h->fb_stalls >= 3) h->fb_mode = 0; }
     feedback_reset(h);
-    if (h->pcg_on) { h->pcg_on = false; h->pcg_fallbacks += 1; }     // only a failed start-up rendezvous stalls the persistent kernel
-    int extra = std::max(2 * h->budget, 8);
-    if (h->prm.kkt_kind == COSMO_HIP_KKT_CG) {
-      CHK(enqueue_clear_stall(h));
-      if (h->cg_sr) CHK(sr_enqueue_iterations(h, 1, h->ctl_host->cg_k, extra));
-      else CHK(enqueue_cg_iterations(h, 1, h->ctl_host->cg_k, extra));
-      CHK(enqueue_tail(h, 1));
-    } else {
-      CHK(enqueue_clear_stall(h));
-      CHK(minres_resume(h, extra));
-    }
+    CHK(kkt_resume(h, std::max(2 * h->budget, 8)));
     CHK(sync_ctl(h));
     h->budget = std::min(4096, std::max(h->budget, h->ctl_host->cg_k + 2));
   }
@@ -1391,7 +1223,7 @@ extern "C" int32_t cosmo_hip_get_iterates(cosmo_hip_handle* h, real* w, real* w_
 
 extern "C" int32_t cosmo_hip_cg_persist_stats(cosmo_hip_handle* h, int64_t out[8]) {
   if (!h || !out) return COSMO_HIP_ERR_INVALID;
-  out[0] = h->pcg_on ? 1 : 0; out[1] = h->pcg_W; out[2] = h->pcg_launches; out[3] = h->pcg_fallbacks;
+  out[0] = h->route == KKT_CG_PERSIST ? 1 : 0; out[1] = h->pcg_W; out[2] = h->pcg_launches; out[3] = h->pcg_fallbacks;
   out[4] = out[5] = out[6] = 0; out[7] = h->pcg_cap;
   if (h->pcg_sync) {                                  // synchronisation words of the last launch: tickets, barrier arrivals, abort flag
     unsigned w[4] = {0, 0, 0, 0};
@@ -1443,7 +1275,6 @@ extern "C" int32_t cosmo_hip_get_stats(cosmo_hip_handle* h, int64_t out[8]) {
 // ---------------------------------------------------------------------------------------------------------------------
 // measurement hooks
 // ---------------------------------------------------------------------------------------------------------------------
-int32_t time_op_apply(cosmo_hip_handle* h, int reps, double* avg_seconds);  // kernels.hip
 
 extern "C" int32_t cosmo_hip_time_spmv(cosmo_hip_handle* h, int32_t which, int32_t reps, double* avg_seconds,
                                        double* algorithmic_bytes) {
@@ -1484,10 +1315,12 @@ extern "C" int32_t cosmo_hip_time_spmv(cosmo_hip_handle* h, int32_t which, int32
 extern "C" int32_t cosmo_hip_time_krylov(cosmo_hip_handle* h, int32_t reps, double* avg_seconds, double* algorithmic_bytes, int32_t* launches_per_iteration) {
   ENTER(h);
   if (!h->have_params || !h->have_iterates || reps <= 0 || !avg_seconds) return cosmo_fail(h, COSMO_HIP_ERR_INVALID, "time_krylov: set up the loop first");
-  if (h->prm.kkt_kind != COSMO_HIP_KKT_CG || (h->cg_sr && !h->op_fold) || h->pcg_on || h->row_shard) return cosmo_fail(h, COSMO_HIP_ERR_UNSUPPORTED, "time_krylov: the CG recurrences of the loop (literal, Jacobi, one-launch single-reduction on the assembled operator) on an unsharded handle only");
+  double bytes = 0.0;
+  int nl = 0;
+  if (!kkt_krylov_model(h, &bytes, &nl) || h->row_shard) return cosmo_fail(h, COSMO_HIP_ERR_UNSUPPORTED, "time_krylov: the CG recurrences of the loop (literal, Jacobi, one-launch single-reduction on the assembled operator) on an unsharded handle only");
   CHK(sync_ctl(h));
   if (h->ctl_host->halt) return cosmo_fail(h, COSMO_HIP_ERR_INVALID, "time_krylov: the loop is halted");
-  const long long n = h->n, m = h->m;
+  const long long n = h->n;
   real* keep = nullptr;
   HIPCHK(h, hipMalloc((void**)&keep, sizeof(real) * (size_t)std::max<long long>(n, 1)));
   HIPCHK(h, hipMemcpyAsync(keep, h->x_tl, sizeof(real) * (size_t)n, hipMemcpyDeviceToDevice, h->stream));
@@ -1495,12 +1328,11 @@ extern "C" int32_t cosmo_hip_time_krylov(cosmo_hip_handle* h, int32_t reps, doub
   HIPCHK(h, hipEventCreate(&e0)); HIPCHK(h, hipEventCreate(&e1));
   const long long sp[3] = {h->spmv_calls[0], h->spmv_calls[1], h->spmv_calls[2]};
   int32_t rc = enqueue_y2_only(h);                             // resets the per-solve flags (y2 = rho .* ls_s is recomputed to the same values)
-  if (rc == COSMO_HIP_OK) rc = enqueue_cg_start(h, 1, R(0.0)); // tolerance 0: every one of the `reps` iterations does full work
-  if (rc == COSMO_HIP_OK && h->cg_sr) rc = sr_enqueue_start(h, 1);
+  if (rc == COSMO_HIP_OK) rc = kkt_enqueue_start(h, 1, R(0.0)); // tolerance 0: every one of the `reps` iterations does full work
   if (rc == COSMO_HIP_OK && hipEventRecord(e0, h->stream) != hipSuccess) rc = cosmo_fail(h, COSMO_HIP_ERR_HIP, "hipEventRecord failed");
   const int likely = h->cg_k_likely;
   h->cg_k_likely = 0x7fffffff;
-  if (rc == COSMO_HIP_OK) rc = h->cg_sr ? sr_enqueue_iterations(h, 1, 0, reps) : enqueue_cg_iterations(h, 1, 0, reps);
+  if (rc == COSMO_HIP_OK) rc = kkt_enqueue_iterations(h, 1, 0, reps);
   h->cg_k_likely = likely;
   if (rc == COSMO_HIP_OK && hipEventRecord(e1, h->stream) != hipSuccess) rc = cosmo_fail(h, COSMO_HIP_ERR_HIP, "hipEventRecord failed");
   if (rc == COSMO_HIP_OK && hipEventSynchronize(e1) != hipSuccess) rc = cosmo_fail(h, COSMO_HIP_ERR_HIP, "hipEventSynchronize failed");
@@ -1514,52 +1346,9 @@ extern "C" int32_t cosmo_hip_time_krylov(cosmo_hip_handle* h, int32_t reps, doub
   h->spmv_calls[0] = sp[0]; h->spmv_calls[1] = sp[1]; h->spmv_calls[2] = sp[2];
   if (rc != COSMO_HIP_OK) return rc;
   *avg_seconds = (double)ms * 1e-3 / reps;
-  double bytes; int nl;
-  if (h->op_fold) {
-    const FoldPlan* f = (const FoldPlan*)h->fold;
-    bytes = 12.0 * (double)f->nnz_full + 4.0 * (n + 1) + 16.0 * n + 8.0 * 10.0 * n;    // B_spmv(M) of the FULLY assembled operator (the unit since round 2; a partially
-                                                                                        // assembled operator streams fewer entries for the same product) + B_cgvec (n-side); Jacobi adds dinv: + 8 n
-    if (h->cg_jacobi) bytes += 8.0 * n;
-    nl = 2;
-    if (h->cg_sr) nl = 1;      // one-launch recurrence: the SAME algorithmic bytes (SURVEY 8d prices a Krylov iteration of the reference: operator + 10 n-vectors; the
-                               // records {r, w, s, p} read and written once by their owners + x read and written are 10 n words too)
-  } else {
-    const CsrDev& Ao = h->op_split ? h->Am : h->A;
-    const CsrDev& PTo = h->op_split ? h->PTm : h->PT;
-    bytes = (12.0 * Ao.nnz + 4.0 * (Ao.nrows + 1) + 8.0 * n + 8.0 * Ao.nrows) + (12.0 * PTo.nnz + 8.0 * (n + 1) + 8.0 * (n + Ao.nrows) + 8.0 * n) + 8.0 * (10.0 * n + m);
-    nl = h->cg_ru ? 3 : 4;
-  }
   if (algorithmic_bytes) *algorithmic_bytes = bytes;
   if (launches_per_iteration) *launches_per_iteration = nl;
   return COSMO_HIP_OK;
-}
-
-extern "C" const char* cosmo_hip_kkt_recurrence(cosmo_hip_handle* h) {
-  if (!h || !h->have_params) return "not set up";
-  static const char* sr_names[] = {"", "k_sr_M<1>", "k_sr_M<2>", "k_sr_M<3>", "k_sr_M<4>", "", "", "", "k_sr_M<8>"};
-  static const char* pair_names[] = {"", "k_cg_dirM<1, false> + k_cg_upd<false>", "k_cg_dirM<2, false> + k_cg_upd<false>", "k_cg_dirM<3, false> + k_cg_upd<false>",
-                                     "k_cg_dirM<4, false> + k_cg_upd<false>", "", "", "", "k_cg_dirM<8, false> + k_cg_upd<false>"};
-  static const char* updf_names[] = {"", "k_cg_dirM<1, false> + k_cg_updF", "k_cg_dirM<2, false> + k_cg_updF", "k_cg_dirM<3, false> + k_cg_updF", "k_cg_dirM<4, false> + k_cg_updF", "", "", "",
-                                     "k_cg_dirM<8, false> + k_cg_updF"};
-  static const char* pc_names[] = {"", "k_cg_dirM<1, true> + k_cg_upd<true>", "k_cg_dirM<2, true> + k_cg_upd<true>", "k_cg_dirM<3, true> + k_cg_upd<true>",
-                                   "k_cg_dirM<4, true> + k_cg_upd<true>", "", "", "", "k_cg_dirM<8, true> + k_cg_upd<true>"};
-  static thread_local char buf[256];
-  if (h->prm.kkt_kind == COSMO_HIP_KKT_DIRECT) return "direct: supernodal LDL' of the full KKT system, one launch per tree level (csrc/ldl.hip)";
-  if (h->prm.kkt_kind == COSMO_HIP_KKT_MINRES) return "minres on the full KKT system (csrc/minres.hip)";
-  if (h->prm.kkt_kind == COSMO_HIP_KKT_MINRES_REDUCED) return "minres on the reduced system (csrc/minres.hip)";
-  const FoldPlan* f = (const FoldPlan*)h->fold;
-  const int sl = (h->op_fold && f) ? ((f->slots >= 1 && f->slots <= 4) ? f->slots : 8) : 0;
-  if (h->pcg_on) return "cg: literal recurrence in one persistent launch (csrc/cg_persist.hip, opt-in)";
-  if (h->cg_jacobi) { snprintf(buf, sizeof buf, "cg: Jacobi-preconditioned recurrence on the assembled operator (opt-in), %s", pc_names[sl]); return buf; }
-  if (h->cg_sr && h->op_fold) {
-    snprintf(buf, sizeof buf, "cg: one-launch single-reduction recurrence on the assembled operator%s, %s", h->cg_sr_auto ? " (lab switch COSMO_HIP_CG_SR_DEFAULT=1)" : " (opt-in kkt_kind CG_SR)", sr_names[sl]);
-    return buf;
-  }
-  if (h->cg_sr) return "cg: single-reduction recurrence, two launches per iteration (kkt_kind CG_SR), k_sr_update_A + k_sr_op";
-  if (h->op_fold && f->nd > 0) { snprintf(buf, sizeof buf, "cg: literal recurrence on the partially assembled operator (%d rows of A kept factored), two launches per iteration, %s", f->nd, updf_names[sl]); return buf; }
-  if (h->op_fold) { snprintf(buf, sizeof buf, "cg: literal recurrence on the assembled operator, two launches per iteration, %s", pair_names[sl]); return buf; }
-  return h->cg_ru ? "cg: literal recurrence, three launches per iteration, k_cg_dirA + k_op_apply + k_cg_upd<false>"
-                  : "cg: literal recurrence, four launches per iteration, k_cg_dir + k_spmv_A_rho + k_op_apply + k_cg_upd<false>";
 }
 
 extern "C" int32_t cosmo_hip_set_profiling(cosmo_hip_handle* h, int32_t on) {

@@ -24,9 +24,6 @@
 #define PARTS(h, slot) ((h)->partials + (size_t)(slot) * COSMO_MAX_PARTIALS)
 
 
-// launch helpers of kernels.hip (every launch stays next to its kernel)
-int32_t launch_cg_upd(cosmo_hip_handle* h, int guard, int k, int n_uc);
-int32_t launch_cg_dir_check(cosmo_hip_handle* h, int guard, int kk, int n_rr);
 static inline int ew_grid(long long N) {
   long long g = (N + COSMO_BS - 1) / COSMO_BS;
   if (g < 1) g = 1;
@@ -397,11 +394,9 @@ static int32_t up(cosmo_hip_handle* h, T** dst, const std::vector<T>& v) {
 // Am: the multi-nonzero rows of A (compact, columns ascending within a row); (prp, pcol, pval): CSR of P.  Called at the end of
 // build_op_split (the split is active and rho_m / diag exist on the device).
 int32_t fold_build(cosmo_hip_handle* h, const HostCsr& Am, const std::vector<int>& prp, const std::vector<int>& pcol,
-                   const std::vector<real>& pval) {
+                   const std::vector<real>& pval, int factor_min) {
   fold_free(h);
-  if (const char* e = getenv("COSMO_HIP_OP_FOLD")) if (e[0] == '0') return COSMO_HIP_OK;
-  if (!h->op_split || h->n <= 0 || (!h->cg_sr && !h->cg_ru)) return COSMO_HIP_OK;     // literal CG: needs the {r, u} records; single-reduction CG: its own records
-  if (const char* e = getenv("COSMO_HIP_CG_PERSIST")) if (atoi(e)) return COSMO_HIP_OK;     // the single-launch lab path keeps the split operator
+  if (h->n <= 0) return COSMO_HIP_OK;
   const long long n = h->n;
   const int mm = Am.nrows;
   const long long nnzP = prp.empty() ? 0 : prp[(size_t)n];
@@ -417,19 +412,16 @@ int32_t fold_build(cosmo_hip_handle* h, const HostCsr& Am, const std::vector<int
   // the 708 k entries of M; partially assembled 107 k + 60 k).  MEASURED (profiles/r06_partial_assembly.txt): k_cg_dirM 7.7 -> 4.9 us -- it is then at the
   // floor of a kernel of this chain, k_cg_upd<false> with next to no data takes the same 4.9 us -- but k_cg_updF 4.9 -> 6.2 us (the dense rows' own
   // col -> gather chain sits BEHIND alpha); per Krylov iteration as the loop enqueues it 11.72 -> 11.30 us, 250.9 -> 253.9 it/s (+1.2 %): below what it costs in
-  // code paths, hence OPT-IN (COSMO_HIP_FOLD_FACTOR=1; COSMO_HIP_FOLD_FACTOR_MIN=len moves the row-length threshold).  The literal recurrence only.
+  // code paths, hence OPT-IN (COSMO_HIP_FOLD_FACTOR=1; COSMO_HIP_FOLD_FACTOR_MIN=len moves the row-length threshold; kkt.hip: factor_min).  The literal
+  // recurrence only.
   std::vector<int> did((size_t)mm, -1);
   int nd = 0;
-  { bool factor = false;                           // OPT-IN (COSMO_HIP_FOLD_FACTOR=1): measured +1.2 % on BASELINE config 5, see below
-    int lmin = 4;
-    if (const char* e = getenv("COSMO_HIP_FOLD_FACTOR")) factor = !h->cg_sr && !h->cg_jacobi && atoi(e) != 0;
-    if (const char* e = getenv("COSMO_HIP_FOLD_FACTOR_MIN")) { const int v = atoi(e); if (v >= 2) lmin = v; }
-    if (factor) {
-      long long part = 0, dense_nnz = 0;
-      for (int r = 0; r < mm; ++r) { const long long len = Am.rowptr[r + 1] - Am.rowptr[r]; if (len >= lmin) { dense_nnz += len; } else part += len * len; }
-      if (dense_nnz > 0 && 2 * (part + 2 * dense_nnz) <= nterms)
-        for (int r = 0; r < mm; ++r) if (Am.rowptr[r + 1] - Am.rowptr[r] >= lmin) did[(size_t)r] = nd++;
-    } }
+  if (factor_min > 0) {
+    long long part = 0, dense_nnz = 0;
+    for (int r = 0; r < mm; ++r) { const long long len = Am.rowptr[r + 1] - Am.rowptr[r]; if (len >= factor_min) { dense_nnz += len; } else part += len * len; }
+    if (dense_nnz > 0 && 2 * (part + 2 * dense_nnz) <= nterms)
+      for (int r = 0; r < mm; ++r) if (Am.rowptr[r + 1] - Am.rowptr[r] >= factor_min) did[(size_t)r] = nd++;
+  }
   // Am' as lists (row of Am, value) per column
   std::vector<int> tp((size_t)n + 1, 0);
   for (int cidx : Am.col) tp[(size_t)cidx + 1]++;
@@ -567,7 +559,7 @@ int32_t fold_refresh(cosmo_hip_handle* h) {
   if (!h->op_fold || !f) return COSMO_HIP_OK;
   hipLaunchKernelGGL(k_fold_refresh, dim3(ew_grid(f->M.nnz)), dim3(COSMO_BS), 0, h->stream, f->M.nnz, f->base, f->drow, f->tptr, f->trow,
                      f->tprod, h->op_rho_m, h->op_diag, h->prm.sigma, f->M.val, (const int*)f->ppos, f->pval);
-  if (h->cg_jacobi)
+  if (h->route == KKT_CG_JACOBI)
     hipLaunchKernelGGL(k_fold_dinv, dim3(ew_grid(h->n)), dim3(COSMO_BS), 0, h->stream, h->n, f->dpos, f->M.val, f->dinv);
   HIPCHK(h, hipGetLastError());
   return COSMO_HIP_OK;
@@ -579,7 +571,7 @@ int32_t fold_enqueue_start(cosmo_hip_handle* h, int guard, real tol_k) {
   prof_begin(h, KC_OP_APPLY);
   if (f->nd > 0)               // partial assembly: (Ad x) for the start residual r0 = rhs - (Ms x + Ad' rho (Ad x))
     hipLaunchKernelGGL(k_ad_dot, dim3(gD), dim3(COSMO_BS), 0, h->stream, h->ctl, guard, view_of(f->Ad), (const real*)h->x_tl, f->tx, (real2*)nullptr);
-  if (h->cg_jacobi)
+  if (h->route == KKT_CG_JACOBI)
     hipLaunchKernelGGL(k_fold_start<true>, dim3(f->M.grid), dim3(COSMO_BS), 0, h->stream, h->ctl, guard, view_of(f->M), h->x_tl, h->rhs, h->r,
                        (real2*)h->cg_ru, PARTS(h, SLOT_RR), PARTS(h, SLOT_BB), h->n_bb, tol_k, (const real*)f->dinv, PARTS(h, SLOT_AUX2), (const real*)nullptr);
   else
@@ -604,7 +596,7 @@ static void fold_launch_pair(cosmo_hip_handle* h, FoldPlan* f, int guard, int k,
 #define LAUNCH_DIRM_(SLN, PCF) hipLaunchKernelGGL((k_cg_dirM<SLN, PCF>), dim3(f->M.grid), dim3(COSMO_BS), 0, h->stream, h->ctl, guard, check_first, k, n, n, \
                          PARTS(h, SLOT_RR), n_rr, view_of(f->M), ru_cur, h->c, h->u, PARTS(h, SLOT_UC), (const real*)PARTS(h, SLOT_AUX2), \
                          (const int*)(f->cap == SLN * COSMO_BS ? f->pcol : nullptr), (const real*)f->pval, (const real2*)f->tt, f->tcur, f->nd)
-#define LAUNCH_DIRM(SLN) do { if (h->cg_jacobi) LAUNCH_DIRM_(SLN, true); else LAUNCH_DIRM_(SLN, false); } while (0)
+#define LAUNCH_DIRM(SLN) do { if (h->route == KKT_CG_JACOBI) LAUNCH_DIRM_(SLN, true); else LAUNCH_DIRM_(SLN, false); } while (0)
   switch (f->slots) {
     case 1: LAUNCH_DIRM(1); break;
     case 2: LAUNCH_DIRM(2); break;

@@ -354,17 +354,13 @@ __global__ void k_pcg_reset(unsigned* sync) { sync[0] = 0u; sync[1] = 0u; sync[2
 #define PCG_NVARIANTS 2
 static const int kPcgVariants[PCG_NVARIANTS][3] = {{2, 4, 2}, {4, 6, 2}};
 
-// Decides whether the handle's CG operator qualifies and prepares the launch; called from set_params after build_op_split.
-int32_t pcg_setup(cosmo_hip_handle* h) {
-  h->pcg_on = false;
-  if (h->pcg_sync) { (void)hipFree(h->pcg_sync); h->pcg_sync = nullptr; }
-  if (h->pcg_u2) { (void)hipFree(h->pcg_u2); h->pcg_u2 = nullptr; }
-  // OPT-IN (COSMO_HIP_CG_PERSIST=1).  Measured on MI355X (profiles/r02_cg_persist.md): bit-identical to the multi-kernel loop, but not
-  // faster -- 18-46 us per Krylov iteration against 16-22 us for four launches: one XCD's L2 has to serve every gather of the
-  // iteration as an uncached (sc1) 8-byte request, and three software barriers cost about what the four kernel boundaries cost.
-  int want = 0;
-  if (const char* e = getenv("COSMO_HIP_CG_PERSIST")) want = atoi(e) ? 1 : 0;
-  if (want == 0 || h->prm.kkt_kind != COSMO_HIP_KKT_CG || h->cg_sr || h->n == 0) return COSMO_HIP_OK;
+// Decides whether the handle's (split or plain) CG operator fits the single launch and prepares it; called by kkt_configure after build_op_split.
+// OPT-IN (COSMO_HIP_CG_PERSIST=1).  Measured on MI355X (profiles/r02_cg_persist.md): bit-identical to the multi-kernel loop, but not
+// faster -- 18-46 us per Krylov iteration against 16-22 us for four launches: one XCD's L2 has to serve every gather of the
+// iteration as an uncached (sc1) 8-byte request, and three software barriers cost about what the four kernel boundaries cost.
+int32_t pcg_setup(cosmo_hip_handle* h, bool* accepted) {
+  pcg_free(h);
+  *accepted = false;
   const CsrDev& Ao = h->op_split ? h->Am : h->A;
   const CsrDev& PTo = h->op_split ? h->PTm : h->PT;
   hipDeviceProp_t prop;
@@ -392,14 +388,13 @@ int32_t pcg_setup(cosmo_hip_handle* h) {
   HIPCHK(h, hipMalloc((void**)&h->pcg_u2, sizeof(real) * (size_t)std::max<long long>(h->n, 1)));
   HIPCHK(h, hipMemset(h->pcg_sync, 0, 16 * sizeof(unsigned)));
   HIPCHK(h, hipMemset(h->pcg_u2, 0, sizeof(real) * (size_t)std::max<long long>(h->n, 1)));
-  h->pcg_on = true;
+  *accepted = true;
   return COSMO_HIP_OK;
 }
 
 void pcg_free(cosmo_hip_handle* h) {
   if (h->pcg_sync) { (void)hipFree(h->pcg_sync); h->pcg_sync = nullptr; }
   if (h->pcg_u2) { (void)hipFree(h->pcg_u2); h->pcg_u2 = nullptr; }
-  h->pcg_on = false;
 }
 
 // the whole Krylov loop of one solve (after enqueue_cg_start); returns without synchronising

@@ -137,7 +137,7 @@ __global__ __launch_bounds__(COSMO_BS) void k_sr_A_plain(const Ctl* __restrict__
 // the NEXT iteration.  Records and partial slots alternate by iteration parity (owners write new ones while others gather old ones).
 //
 // Round 6 measured this form as a candidate DEFAULT of kkt_kind CG on assembled operators (the reference's cg! lives in a package outside its
-// tree, kktsolver_indirect.jl:66-74, and SURVEY 8(c) defines KKT parity as the residual bound) and rejected it: see api.hip: choose_cg_recurrence.
+// tree, kktsolver_indirect.jl:66-74, and SURVEY 8(c) defines KKT parity as the residual bound) and rejected it: see kkt.hip: kkt_configure.
 // The kernel has the load-first structure of k_cg_dirM: everything that does not depend on (alpha, beta) -- both partial sets, the tile
 // descriptor, (col, val) and the 24-byte gathers of the first tile, the row pointers, the thread's own record and x -- is requested before
 // the scalar work; the iteration index of a launch inside a captured chain comes from ctl->sr_k[parity].
@@ -267,7 +267,6 @@ __global__ __launch_bounds__(COSMO_BS) void k_sr_M_init(const Ctl* __restrict__ 
 // ---------------------------------------------------------------------------------------------------------------------
 int32_t sr_alloc(cosmo_hip_handle* h) {
   if (h->sr_rec) { (void)hipFree(h->sr_rec); h->sr_rec = nullptr; }
-  if (!h->cg_sr) return COSMO_HIP_OK;
   const size_t bytes = 2 * sizeof(SrRec) * (size_t)std::max<long long>(h->n, 1);
   HIPCHK(h, hipMalloc((void**)&h->sr_rec, bytes));
   HIPCHK(h, hipMemsetAsync(h->sr_rec, 0, bytes, h->stream));
@@ -283,7 +282,7 @@ static inline int sr_grid1(const cosmo_hip_handle* h, const CsrDev& Ao) {
 
 // after enqueue_cg_start (r0 = rhs - L x0 in h->r, its r'r partials in SLOT_RR, tolerance set): w0 = L r0, records, w0'r0 partials
 int32_t sr_enqueue_start(cosmo_hip_handle* h, int guard) {
-  if (h->op_fold) {                     // assembled operator: one product (k_fold_start left r0 in h->r, its r'r partials in SLOT_RR)
+  if (h->route == KKT_CG_SR_M) {        // assembled operator: one product (k_fold_start left r0 in h->r, its r'r partials in SLOT_RR)
     FoldPlan* f = (FoldPlan*)h->fold;
     prof_begin(h, KC_OP_APPLY);
     hipLaunchKernelGGL(k_sr_M_init, dim3(f->M.grid), dim3(COSMO_BS), 0, h->stream, h->ctl, guard, view_of(f->M), (const real*)h->r, (SrRec*)h->sr_rec,
@@ -367,7 +366,7 @@ static bool sr_chain_ready(cosmo_hip_handle* h, FoldPlan* f) {
 
 int32_t sr_enqueue_iterations(cosmo_hip_handle* h, int guard, int k_begin, int count) {
   const long long n = h->n;
-  if (h->op_fold) {                     // ONE launch per Krylov iteration on the assembled operator
+  if (h->route == KKT_CG_SR_M) {        // ONE launch per Krylov iteration on the assembled operator
     FoldPlan* f = (FoldPlan*)h->fold;
     SrRec* rec = (SrRec*)h->sr_rec;
     const int G = f->M.grid;

@@ -223,7 +223,6 @@ extern "C" int32_t cosmo_hip_comm_stats_ex(cosmo_hip_handle* h, int64_t out[8]) 
 // first_cone: nranks+1 non-decreasing cone indices, first_cone[0] = 0, first_cone[nranks] = ncones.  Rank r projects the
 // SOC / PSD cones first_cone[r] <= k < first_cone[r+1]; Zero / Nonnegatives / Box rows are projected by everyone (they are
 // part of the elementwise copy kernel).  Must be called after cosmo_hip_set_cones (rebuilds the SOC table and PSD plan).
-int32_t rebuild_cone_plans(cosmo_hip_handle* h);   // api.hip
 // boundaries -> CommState (first_cone, row_lo / row_hi of every rank), validated against the composite set currently installed
 int32_t comm_set_partition(cosmo_hip_handle* h, const int64_t* first_cone, const char* who) {
   if (!h->comm) return cosmo_fail(h, COSMO_HIP_ERR_INVALID, "%s: comm_init first", who);

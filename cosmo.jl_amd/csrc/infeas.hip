@@ -10,9 +10,6 @@
 #include <math.h>
 #include <vector>
 
-int32_t sync_ctl(cosmo_hip_handle* h);
-int32_t psd_extreme_eigs(cosmo_hip_handle* h, const real* vec, real sign, real tol, std::vector<real>& lam_min);   // psd.hip
-
 // delta_y capture at the top of the iteration: dy = rho .* (w_prev_s - s)            (solver.jl:145-148)
 __global__ __launch_bounds__(COSMO_BS) void k_inf_capture(const Ctl* __restrict__ ctl, long long n, long long m,
                                                           const real* __restrict__ w_prev, const real* __restrict__ s,

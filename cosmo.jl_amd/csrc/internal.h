@@ -139,6 +139,22 @@ enum KernelClass {
   KC_CHK_PRIM, KC_CHK_DUAL, KC_CHK_FINAL, KC_RHO_APPLY, KC_MINRES_VEC, KC_OTHER
 };
 
+// The route of a handle's KKT solves: solver, recurrence and operator form, decided once by kkt_configure (kkt.hip)
+enum KktRoute {
+  KKT_NONE = 0,
+  KKT_DIRECT,             // supernodal LDL' of the full system (ldl.hip)
+  KKT_MINRES_FULL,        // MINRES on the full system (minres.hip)
+  KKT_MINRES_REDUCED,     // MINRES on the reduced system (minres.hip)
+  KKT_CG_PERSIST,         // literal CG in one persistent launch per solve (cg_persist.hip); falls back to KKT_CG_FUSED / KKT_CG_PLAIN
+  KKT_CG_JACOBI,          // Jacobi-preconditioned CG on the assembled operator (cg_fold.hip)
+  KKT_CG_SR_M,            // single-reduction CG, one launch per iteration on the assembled operator (cg_sr.hip: k_sr_M)
+  KKT_CG_SR,              // single-reduction CG, two launches per iteration (cg_sr.hip)
+  KKT_CG_FOLD_PARTIAL,    // literal CG on the partially assembled operator, two launches per iteration (cg_fold.hip: k_cg_updF)
+  KKT_CG_FOLD,            // literal CG on the assembled operator, two launches per iteration (cg_fold.hip)
+  KKT_CG_FUSED,           // literal CG, three launches per iteration (kernels.hip: k_cg_dirA)
+  KKT_CG_PLAIN            // literal CG, four launches per iteration (kernels.hip)
+};
+
 struct ConeTable {  // host copy of the composite set
   std::vector<int32_t> type;
   std::vector<int64_t> dim, off;
@@ -175,7 +191,7 @@ struct cosmo_hip_handle {
   int *op_sc_ptr = nullptr, *op_sc_row = nullptr;
   real *op_sc_a2 = nullptr, *op_diag = nullptr, *op_rho_m = nullptr;
   long long op_nsingle = 0;
-  // assembled reduced operator M = P + diag(sigma + d) + Am' rho_m Am (cg_fold.hip): two launches per Krylov iteration
+  // assembled reduced operator M = P + diag(sigma + d) + Am' rho_m Am (cg_fold.hip)
   bool op_fold = false;
   void* fold = nullptr;           // FoldPlan
   // data vectors
@@ -205,14 +221,11 @@ struct cosmo_hip_handle {
   void* psd_polar = nullptr;      // PolarPlan (psd_polar.hip): large cones
   void* accel = nullptr;          // AaState (anderson.hip)
   long long safeguarding_iter = 0;
-  bool cg_sr = false;             // single-reduction (Chronopoulos-Gear) CG, cg_sr.hip: kkt_kind COSMO_HIP_KKT_CG_SR (or the lab switch behind cg_sr_auto)
-  bool cg_sr_auto = false;        // lab switch COSMO_HIP_CG_SR_DEFAULT=1: kkt_kind CG took the one-launch recurrence on an assembled operator (measured and rejected as the default, api.hip: choose_cg_recurrence)
   long long auto_rho_fixed_at = -1;   // iteration at which the automatic rho interval (adaptive_rho_interval == 0, solver.jl:244-256) was fixed; -1: not (yet)
-  bool cg_jacobi = false;  // kkt_kind CG_JACOBI: opt-in Jacobi-preconditioned CG on the assembled operator (cg_fold.hip)
+  KktRoute route = KKT_NONE;      // how the KKT solves run (kkt.hip: kkt_configure)
   void* sr_rec = nullptr;         // 2 n records {r, w, s, p}
   real* cg_ru = nullptr;        // {r_i, u_i} interleaved (2n doubles): operands of the fused direction + A-product kernel (k_cg_dirA); null = unfused
   // persistent single-launch CG (cg_persist.hip)
-  bool pcg_on = false;
   unsigned* pcg_sync = nullptr;
   real* pcg_u2 = nullptr;
   int pcg_W = 0, pcg_cap = 0;
@@ -289,39 +302,74 @@ int32_t cosmo_fail(cosmo_hip_handle* h, int32_t code, const char* fmt, ...);
     if (rc__ != COSMO_HIP_OK) return rc__; \
   } while (0)
 
-// ---- launch helpers implemented in kernels.hip ---------------------------------------------------------------------
-void build_row_blocks(const std::vector<int>& rowptr, int nrows, std::vector<int>& rb, int tile_override);   // api.hip: row boundaries of the CSR-stream tiles
+// ---- api.hip ------------------------------------------------------------------------------------------------------
+void build_row_blocks(const std::vector<int>& rowptr, int nrows, std::vector<int>& rb, int tile_override);   // row boundaries of the CSR-stream tiles
 // tile_override > 0: nonzeros per CSR-stream tile (<= COSMO_NNZ_PER_BLOCK) instead of the size heuristic of build_row_blocks
 int32_t upload_csr(cosmo_hip_handle* h, const HostCsr& M, CsrDev& D, int split_col, int tile_override = 0);
 void free_csr(CsrDev& D);
 void prof_begin(cosmo_hip_handle* h, int kc);
 void prof_end(cosmo_hip_handle* h);
 int32_t prof_collect(cosmo_hip_handle* h);
+int32_t sync_ctl(cosmo_hip_handle* h);
+int32_t rebuild_cone_plans(cosmo_hip_handle* h);
+int32_t reclassify_after_scaling(cosmo_hip_handle* h);
+int32_t solve_budget(cosmo_hip_handle* h, int* budget_out);     // Krylov budget of the next loop solve
+int32_t feedback_record(cosmo_hip_handle* h);                   // its Krylov count, copied back behind the solve
 
-// CG operator split
-int32_t build_op_split(cosmo_hip_handle* h, bool force = false);
-int32_t choose_cg_recurrence(cosmo_hip_handle* h);      // api.hip: kkt_kind CG on an assembled operator -> the one-launch recurrence of cg_sr.hip
-int32_t refresh_op_split(cosmo_hip_handle* h);
+// CG operator split (api.hip); any_a: build the split for any A (row sharding), fold: assemble it where sparse enough (cg_fold.hip),
+// keeping the rows of A with >= factor_min nonzeros factored (0: none)
+int32_t build_op_split(cosmo_hip_handle* h, bool any_a, bool fold, int factor_min);
+int32_t refresh_op_split(cosmo_hip_handle* h);   // kernels.hip
 void free_op_split(cosmo_hip_handle* h);
+
+// ---- KKT solve routes (kkt.hip) ------------------------------------------------------------------------------------
+int32_t kkt_configure(cosmo_hip_handle* h, bool force_split);   // set_params (force_split: set_row_shard)
+void kkt_free(cosmo_hip_handle* h);
+int32_t kkt_update_rho(cosmo_hip_handle* h);                    // after a new rho vector was uploaded
+int32_t kkt_enqueue_refresh(cosmo_hip_handle* h);               // behind the loop's adaptive-rho check (no-ops unless rho changed)
+int32_t kkt_enqueue_start(cosmo_hip_handle* h, int guard, real tol_k);
+int32_t kkt_enqueue_iterations(cosmo_hip_handle* h, int guard, int k_begin, int count);
+int32_t kkt_enqueue_loop_solve(cosmo_hip_handle* h);            // after k_rhs
+int32_t kkt_solve_now(cosmo_hip_handle* h);                     // ls_x / ls_s uploaded; synchronises
+int32_t kkt_resume(cosmo_hip_handle* h, int extra);             // a stalled loop solve
+bool kkt_krylov_model(const cosmo_hip_handle* h, double* bytes, int* launches);   // time_krylov: false if the route is not timed
+
+// ---- kernels.hip ---------------------------------------------------------------------------------------------------
+int32_t launch_project_simple_inplace(cosmo_hip_handle* h, real* s);
+int32_t launch_z(cosmo_hip_handle* h, int guard);
+int32_t launch_soc(cosmo_hip_handle* h, real* s, int guard);
+int32_t launch_set_w(cosmo_hip_handle* h, const real* x0, const real* s0, const real* mu0);
+int32_t launch_recover_mu(cosmo_hip_handle* h);
+int32_t launch_rho_from_classes(cosmo_hip_handle* h, real rho0);
+int32_t launch_spmv_plain(cosmo_hip_handle* h, const CsrDev& M, const real* x, real* y);   // plain y = M x (fine-grained ABI + building block)
+int32_t launch_spmv_A_rho(cosmo_hip_handle* h, int guard, int mode, const real* v, real* out);
+int32_t launch_reduced_rhs(cosmo_hip_handle* h, int guard, real* out_rhs);
+int32_t launch_cg_upd(cosmo_hip_handle* h, int guard, int k, int n_uc);
+int32_t launch_cg_dir_check(cosmo_hip_handle* h, int guard, int kk, int n_rr);
+int32_t enqueue_cg_rhs(cosmo_hip_handle* h, int guard);                       // rhs = A' y2 + ls_x of a CG solve
+int32_t enqueue_cg_start(cosmo_hip_handle* h, int guard, real tol_k);         // r0 of the literal recurrence on the split or plain operator
+int32_t enqueue_cg_iterations(cosmo_hip_handle* h, int guard, int k_begin, int count);
+int32_t enqueue_rhs(cosmo_hip_handle* h, int guard);
+int32_t enqueue_y2_only(cosmo_hip_handle* h);
+int32_t enqueue_tail(cosmo_hip_handle* h, int loop_mode);
+int32_t enqueue_count_solve(cosmo_hip_handle* h);
+int32_t enqueue_clear_stall(cosmo_hip_handle* h);
+int32_t enqueue_check(cosmo_hip_handle* h, int guard, int mode);
+int32_t time_op_apply(cosmo_hip_handle* h, int reps, double* avg_seconds);
 
 // assembled reduced operator (cg_fold.hip)
 int32_t fold_build(cosmo_hip_handle* h, const HostCsr& Am, const std::vector<int>& prp, const std::vector<int>& pcol,
-                   const std::vector<real>& pval);
+                   const std::vector<real>& pval, int factor_min);
 int32_t fold_refresh(cosmo_hip_handle* h);
 void fold_free(cosmo_hip_handle* h);
 int32_t fold_enqueue_start(cosmo_hip_handle* h, int guard, real tol_k);
 int32_t fold_enqueue_iterations(cosmo_hip_handle* h, int guard, int k_begin, int count);
 
-// plain y = M x (fine-grained ABI + building block)
-int32_t launch_spmv_plain(cosmo_hip_handle* h, const CsrDev& M, const real* x, real* y);
-
-// loop pieces (loop.hip)
-int32_t enqueue_projection(cosmo_hip_handle* h, const real* src, real* dst, real* w_prev_dst,
-                           const real* w_src, bool in_loop);
-int32_t enqueue_admm_x_and_w(cosmo_hip_handle* h);
-int32_t sync_ctl(cosmo_hip_handle* h);
-
-int32_t comm_allreduce_flag(cosmo_hip_handle* h, int* flag);   // comm.hip: max over the ranks of a 0/1 flag
+// MINRES (minres.hip)
+int32_t minres_alloc(cosmo_hip_handle* h);
+int32_t minres_enqueue_solve(cosmo_hip_handle* h, int guard, bool from_loop);
+int32_t minres_resume(cosmo_hip_handle* h, int extra);
+int32_t launch_mr_tail_full(cosmo_hip_handle* h, int loop_mode, const real* xsol);
 
 // direct KKT solver (ldl.hip)
 int32_t ldl_setup(cosmo_hip_handle* h, const std::vector<int64_t>& perm_req);
@@ -343,12 +391,13 @@ bool batch_multi_needs_ext(const cosmo_hip_batch* b);
 int32_t batch_multi_optimize(cosmo_hip_batch** bs, int count, bool ext, cosmo_hip_result* results);
 
 // persistent CG (cg_persist.hip)
-int32_t pcg_setup(cosmo_hip_handle* h);
+int32_t pcg_setup(cosmo_hip_handle* h, bool* accepted);   // *accepted: the operator fits the single launch
 void pcg_free(cosmo_hip_handle* h);
 int32_t pcg_enqueue_solve(cosmo_hip_handle* h, int guard);
 
 // Anderson acceleration (anderson.hip)
 void aa_free(cosmo_hip_handle* h);
+bool aa_get_params(const cosmo_hip_handle* h, cosmo_hip_accel_params* out);
 bool aa_enabled(const cosmo_hip_handle* h);
 bool aa_safeguarded(const cosmo_hip_handle* h);
 bool aa_active(const cosmo_hip_handle* h);
@@ -386,11 +435,14 @@ int32_t polar_adapt(cosmo_hip_handle* h);   // host-side schedule adaptation at 
 bool polar_has_batch(const cosmo_hip_handle* h);
 bool polar_has_large(const cosmo_hip_handle* h);
 
+int32_t polar_complex_is_pd(cosmo_hip_handle* h, const real* vec, real sign, real tol, std::vector<int>& ok);
+
 // PSD projection (psd.hip)
 int32_t psd_plan_create(cosmo_hip_handle* h);
 void psd_plan_destroy(cosmo_hip_handle* h);
 int32_t psd_enqueue_project(cosmo_hip_handle* h, real* s, bool guard);
 int32_t psd_get_ranks(cosmo_hip_handle* h, int64_t* rank_per_cone);
+int32_t psd_extreme_eigs(cosmo_hip_handle* h, const real* vec, real sign, real tol, std::vector<real>& lam_min);
 static inline bool cone_owned(const cosmo_hip_handle* h, long long k) { return h->cone_hi < 0 || (k >= h->cone_lo && k < h->cone_hi); }
 // infeas.hip
 int32_t infeas_enqueue_capture(cosmo_hip_handle* h);
@@ -402,9 +454,11 @@ int32_t comm_allreduce_sum(cosmo_hip_handle* h, real* buf, size_t count);     //
 int32_t comm_allreduce_host(cosmo_hip_handle* h, double* vals, int count, int op /*0 sum, 1 max*/);   // synchronous, host scalars
 int comm_nranks(const cosmo_hip_handle* h);
 int comm_rank(const cosmo_hip_handle* h);
+int32_t comm_allreduce_flag(cosmo_hip_handle* h, int* flag);   // max over the ranks of a 0/1 flag
+int32_t comm_set_partition(cosmo_hip_handle* h, const int64_t* first_cone, const char* who);
+void comm_my_range(const cosmo_hip_handle* h, long long* cone_lo, long long* cone_hi, long long* row_lo, long long* row_hi);
 // rowshard.hip
-int32_t rs_enqueue_cg_rhs(cosmo_hip_handle* h, int guard);
-int32_t rs_enqueue_check(cosmo_hip_handle* h, int guard, int mode);
+int32_t rs_enqueue_cg_rhs(cosmo_hip_handle* h, int guard);   // kernels.hip
 int32_t rs_get_iterates(cosmo_hip_handle* h, real* w, real* w_prev, real* s, real* mu);
 void rs_free(cosmo_hip_handle* h);
 extern "C" int32_t cosmo_hip_comm_destroy(cosmo_hip_handle* h);

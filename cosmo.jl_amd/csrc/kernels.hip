@@ -791,10 +791,9 @@ int32_t launch_rho_from_classes(cosmo_hip_handle* h, real rho0) {
   return COSMO_HIP_OK;
 }
 
-// ---- reduced-system CG solve, enqueued without host synchronisation --------------------------------------------------
-// from_loop: rhs comes from the loop state (k_rhs) and the tail updates w; otherwise ls_x/ls_s were uploaded.
+// ---- reduced-system CG solve on the split or plain operator, enqueued without host synchronisation ----------------------------------
+// (the assembled operator: cg_fold.hip; the route picks the recurrence, kkt.hip)
 int32_t enqueue_cg_iterations(cosmo_hip_handle* h, int guard, int k_begin, int count) {
-  if (h->op_fold) return fold_enqueue_iterations(h, guard, k_begin, count);      // assembled operator: two launches per iteration
   const long long n = h->n;
   const int gE = ew_grid(n);
   const CsrDev& Ao = h->op_split ? h->Am : h->A;
@@ -854,17 +853,17 @@ int32_t rs_enqueue_cg_rhs(cosmo_hip_handle* h, int guard) {
   return COSMO_HIP_OK;
 }
 
+int32_t enqueue_cg_rhs(cosmo_hip_handle* h, int guard) {
+  if (h->row_shard) return rs_enqueue_cg_rhs(h, guard);
+  prof_begin(h, KC_SPMV_AT);
+  hipLaunchKernelGGL(k_cg_rhs, dim3(h->AT.grid), dim3(COSMO_BS), 0, h->stream, h->ctl, guard, view_of(h->AT), h->y2,
+                     h->ls_x, h->rhs, PARTS(h, SLOT_BB));
+  prof_end(h);
+  h->n_bb = h->AT.grid;
+  return COSMO_HIP_OK;
+}
+
 int32_t enqueue_cg_start(cosmo_hip_handle* h, int guard, real tol_k) {
-  if (h->row_shard) {
-    CHK(rs_enqueue_cg_rhs(h, guard));
-  } else {
-    prof_begin(h, KC_SPMV_AT);
-    hipLaunchKernelGGL(k_cg_rhs, dim3(h->AT.grid), dim3(COSMO_BS), 0, h->stream, h->ctl, guard, view_of(h->AT), h->y2,
-                       h->ls_x, h->rhs, PARTS(h, SLOT_BB));
-    prof_end(h);
-    h->n_bb = h->AT.grid;
-  }
-  if (h->op_fold) return fold_enqueue_start(h, guard, tol_k);
   const CsrDev& Ao = h->op_split ? h->Am : h->A;
   const CsrDev& PTo = h->op_split ? h->PTm : h->PT;
   prof_begin(h, KC_SPMV_A);
@@ -969,8 +968,7 @@ int32_t enqueue_check(cosmo_hip_handle* h, int guard, int mode) {
     if (h->row_shard)
       hipLaunchKernelGGL(k_rs_rho_g, dim3(ew_grid(h->m_g > 0 ? h->m_g : 1)), dim3(COSMO_BS), 0, h->stream, h->ctl, guard, h->m_g, h->rho_cls_g,
                          h->prm.rho_min, h->prm.rho_eq_over_rho_ineq, h->rho_g);
-    CHK(refresh_op_split(h));      // rho may have changed on the device: the diagonal part of A' rho A follows (cheap, unconditional)
-    if (h->ldl) CHK(ldl_enqueue_refactor(h, 1));   // direct KKT solver: refill + refactorise, each launch a no-op unless rho changed
+    CHK(kkt_enqueue_refresh(h));   // rho may have changed on the device: the reduced operator or the direct solver's factor follows
     prof_end(h);
   }
   h->spmv_calls[0] += 1; h->spmv_calls[1] += 1; h->spmv_calls[2] += 1;
@@ -1015,7 +1013,7 @@ int32_t refresh_op_split(cosmo_hip_handle* h) {
 // launch helpers used by cg_fold.hip
 int32_t launch_cg_upd(cosmo_hip_handle* h, int guard, int k, int n_uc) {
   prof_begin(h, KC_CG_UPD);
-  if (h->cg_jacobi)
+  if (h->route == KKT_CG_JACOBI)
     hipLaunchKernelGGL(k_cg_upd<true>, dim3(ew_grid(h->n)), dim3(COSMO_BS), 0, h->stream, h->ctl, guard, k, h->n, PARTS(h, SLOT_UC), n_uc, h->u, h->c,
                        h->x_tl, h->r, PARTS(h, SLOT_RR), (real2*)h->cg_ru, (const real*)((FoldPlan*)h->fold)->dinv, PARTS(h, SLOT_AUX2));
   else

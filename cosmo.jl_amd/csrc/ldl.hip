@@ -26,10 +26,6 @@
 #include <chrono>
 #include <math.h>
 
-int32_t launch_mr_tail_full(cosmo_hip_handle* h, int loop_mode, const real* xsol);   // minres.hip
-int32_t enqueue_y2_only(cosmo_hip_handle* h);
-int32_t enqueue_count_solve(cosmo_hip_handle* h);
-
 #define LDL_BS 256
 
 struct LdlPlan {

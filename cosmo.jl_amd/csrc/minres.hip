@@ -15,13 +15,6 @@
 #include <algorithm>
 #include <math.h>
 
-int32_t enqueue_tail(cosmo_hip_handle* h, int loop_mode);
-int32_t enqueue_count_solve(cosmo_hip_handle* h);
-int32_t sync_ctl(cosmo_hip_handle* h);
-int32_t launch_spmv_A_rho(cosmo_hip_handle* h, int guard, int mode, const real* v, real* out);
-int32_t launch_reduced_rhs(cosmo_hip_handle* h, int guard, real* out_rhs);
-int32_t enqueue_y2_only(cosmo_hip_handle* h);
-
 // state slot layout inside Ctl::minres (two slots of 8 doubles, indexed by iteration parity)
 enum { MS_H1 = 0, MS_CP, MS_SP, MS_CC, MS_SC, MS_RHS0, MS_RES, MS_PAD };
 
@@ -276,7 +269,7 @@ int32_t minres_alloc(cosmo_hip_handle* h) {
 
 static MrVecs vecs_of(cosmo_hip_handle* h) {
   MrVecs V;
-  const bool full = h->prm.kkt_kind == COSMO_HIP_KKT_MINRES;
+  const bool full = h->route == KKT_MINRES_FULL;
   const long long NN = h->n + h->m;
   V.N = full ? NN : h->n;
   for (int i = 0; i < 3; ++i) { V.v[i] = h->mr + (size_t)i * NN; V.w[i] = h->mr + (size_t)(3 + i) * NN; }
@@ -288,7 +281,7 @@ static MrVecs vecs_of(cosmo_hip_handle* h) {
 // operator apply y = L v for either system; partial slots: SLOT_UC (top) and SLOT_AUX1 (bottom, full system only)
 static int32_t enqueue_mr_apply(cosmo_hip_handle* h, int guard, int mode, int it, const MrVecs& V, const real* v, const real* vprev,
                                 real* vout) {
-  const bool full = h->prm.kkt_kind == COSMO_HIP_KKT_MINRES;
+  const bool full = h->route == KKT_MINRES_FULL;
   const long long n = h->n;
   prof_begin(h, KC_OP_APPLY);
   if (!full) {
@@ -311,7 +304,7 @@ static int32_t enqueue_mr_apply(cosmo_hip_handle* h, int guard, int mode, int it
 
 static int npart_apply(const cosmo_hip_handle* h) {
   if (h->row_shard) return h->PTm.grid;                  // reduced MINRES on the split operator
-  return h->PT.grid + ((h->prm.kkt_kind == COSMO_HIP_KKT_MINRES) ? (h->A.grid > 0 ? h->A.grid : 1) : 0);
+  return h->PT.grid + ((h->route == KKT_MINRES_FULL) ? (h->A.grid > 0 ? h->A.grid : 1) : 0);
 }
 
 int32_t minres_enqueue_iterations(cosmo_hip_handle* h, int guard, int it_begin, int count) {
@@ -336,7 +329,7 @@ int32_t minres_enqueue_iterations(cosmo_hip_handle* h, int guard, int it_begin, 
 
 static int32_t enqueue_mr_tail(cosmo_hip_handle* h, int loop_mode) {
   const MrVecs V = vecs_of(h);
-  if (h->prm.kkt_kind == COSMO_HIP_KKT_MINRES) {
+  if (h->route == KKT_MINRES_FULL) {
     prof_begin(h, KC_TAIL);
     hipLaunchKernelGGL(k_mr_tail_full, dim3(ewg(h->n + h->m)), dim3(COSMO_BS), 0, h->stream, h->ctl, loop_mode, h->n, h->m, h->prm.alpha,
                        V.x, h->rho, h->s, h->x_tl, h->nu, h->s_tl, h->w);
@@ -368,7 +361,7 @@ int32_t minres_resume(cosmo_hip_handle* h, int extra) {
 // y2 = rho .* ls_s has been formed by the caller.
 int32_t minres_enqueue_solve(cosmo_hip_handle* h, int guard, bool from_loop) {
   const MrVecs V = vecs_of(h);
-  const bool full = h->prm.kkt_kind == COSMO_HIP_KKT_MINRES;
+  const bool full = h->route == KKT_MINRES_FULL;
   const real tol_k = h->prm.tol_constant / pow((real)(h->host_solves + 1), h->prm.tol_exponent);
   if (!from_loop) CHK(enqueue_y2_only(h));
   if (full) {

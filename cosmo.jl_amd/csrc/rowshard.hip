@@ -24,13 +24,6 @@
 #include <vector>
 #include "device_utils.h"
 
-int32_t rebuild_cone_plans(cosmo_hip_handle* h);                                                     // api.hip
-int32_t comm_set_partition(cosmo_hip_handle* h, const int64_t* first_cone, const char* who);         // comm.hip
-void comm_my_range(const cosmo_hip_handle* h, long long* cone_lo, long long* cone_hi, long long* row_lo, long long* row_hi);
-int32_t launch_recover_mu(cosmo_hip_handle* h);                                                      // kernels.hip
-bool aa_get_params(const cosmo_hip_handle* h, cosmo_hip_accel_params* out);                          // anderson.hip
-void aa_free(cosmo_hip_handle* h);
-
 template <class T>
 static int32_t rs_alloc(cosmo_hip_handle* h, T** p, size_t count) {
   *p = nullptr;
@@ -72,10 +65,10 @@ extern "C" int32_t cosmo_hip_set_row_shard(cosmo_hip_handle* h, const int64_t* f
   if (hipSetDevice(h->device) != hipSuccess) return cosmo_fail(h, COSMO_HIP_ERR_HIP, "hipSetDevice failed");
   if (!h->have_params) return cosmo_fail(h, COSMO_HIP_ERR_INVALID, "set_row_shard: set_params first (the reduced operator is built from the whole A)");
   if (h->row_shard) return cosmo_fail(h, COSMO_HIP_ERR_INVALID, "set_row_shard: already row-sharded");
-  if (h->prm.kkt_kind == COSMO_HIP_KKT_DIRECT)
+  if (h->route == KKT_DIRECT)
     return cosmo_fail(h, COSMO_HIP_ERR_UNSUPPORTED, "set_row_shard: the direct KKT solver (kkt_kind DIRECT) factorises the whole KKT matrix on one device; "
                       "a sharded factorisation is not implemented");
-  if (h->prm.kkt_kind != COSMO_HIP_KKT_CG && h->prm.kkt_kind != COSMO_HIP_KKT_MINRES_REDUCED)
+  if (h->route == KKT_MINRES_FULL)
     return cosmo_fail(h, COSMO_HIP_ERR_UNSUPPORTED, "set_row_shard: the solvers of the REDUCED system only (kkt_kind CG / CG_SR / CG_JACOBI / MINRES_REDUCED); "
                       "MINRES on the full KKT system would need an all-reduce per operator application");
   cosmo_hip_accel_params accel_prm;
@@ -89,9 +82,8 @@ extern "C" int32_t cosmo_hip_set_row_shard(cosmo_hip_handle* h, const int64_t* f
 
   // 1. the reduced operator must not depend on h->A / h->rho: force the split form (Am = rows with >= 2 nonzeros, diagonal from the
   //    singleton rows; assembled where sparse enough) and stop the single-launch CG, whose operands are sized at set_params time
-  if (!h->op_split) { CHK(build_op_split(h, true)); CHK(choose_cg_recurrence(h)); }
+  CHK(kkt_configure(h, true));
   if (!h->op_split) return cosmo_fail(h, COSMO_HIP_ERR_UNSUPPORTED, "set_row_shard: no split form of the reduced operator (empty A?)");
-  if (h->pcg_on) { pcg_free(h); h->pcg_on = false; }
 
   // 2. local matrices from the device copies (scaled, if cosmo_hip_scale_ruiz ran)
   std::vector<int> arp, acol;

@@ -10,8 +10,6 @@
 #include <algorithm>
 #include <vector>
 
-int32_t reclassify_after_scaling(cosmo_hip_handle* h);   // api.hip
-
 namespace {
 
 // v[col] = max(v[col], |val|) over every stored entry: non-negative doubles order like their bit patterns, so an integer
