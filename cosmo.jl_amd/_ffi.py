@@ -153,6 +153,12 @@ SIGNATURES = {
     "cosmo_hip_batch_set_direct": (C.c_int32, [C.c_void_p, C.c_int32, _PI64]),
     "cosmo_hip_batch_direct_info": (C.c_int32, [C.c_void_p, _PI64]),
     "cosmo_hip_batch_direct_counts": (C.c_int32, [C.c_void_p, _PI64]),
+    "cosmo_hip_batch_set_scaling_full": (C.c_int32, [C.c_void_p, C.c_int64, _PR, _PR, _PR, _PR, C.c_double, C.c_double]),
+    "cosmo_hip_batch_stage_qb": (C.c_int32, [C.c_void_p, C.c_int64, _PR, _PR]),
+    "cosmo_hip_batch_apply_updates": (C.c_int32, [C.c_void_p]),
+    "cosmo_hip_batch_update_qb": (C.c_int32, [C.c_void_p, C.c_int64, _PI64, _PR, _PR]),
+    "cosmo_hip_batch_warm_restart": (C.c_int32, [C.c_void_p]),
+    "cosmo_hip_batch_get_qb": (C.c_int32, [C.c_void_p, C.c_int64, _PR, _PR]),
     "cosmo_hip_batch_group_create": (C.c_int32, [C.POINTER(C.c_void_p), C.c_int32, C.c_int64]),
     "cosmo_hip_batch_group_destroy": (C.c_int32, [C.c_void_p]),
     "cosmo_hip_batch_group_last_error": (C.c_char_p, [C.c_void_p]),
@@ -171,6 +177,10 @@ SIGNATURES = {
     "cosmo_hip_batch_group_get_iterates": (C.c_int32, [C.c_void_p, C.c_int64, _PR, _PR, _PR, _PR]),
     "cosmo_hip_batch_group_get_counters": (C.c_int32, [C.c_void_p, _PI64]),
     "cosmo_hip_batch_group_get_accel_stats": (C.c_int32, [C.c_void_p, _PI64]),
+    "cosmo_hip_batch_group_stage_qb": (C.c_int32, [C.c_void_p, C.c_int64, _PR, _PR]),
+    "cosmo_hip_batch_group_apply_updates": (C.c_int32, [C.c_void_p]),
+    "cosmo_hip_batch_group_warm_restart": (C.c_int32, [C.c_void_p]),
+    "cosmo_hip_batch_group_get_qb": (C.c_int32, [C.c_void_p, C.c_int64, _PR, _PR]),
 }
 
 
@@ -680,8 +690,37 @@ class Batch:
     def set_scaling(self, k, Dinv, Einv, cinv):
         self._chk(self.lib.cosmo_hip_batch_set_scaling(self._b, int(k), _dp(self._f(Dinv, self.n)), _dp(self._f(Einv, self.m)), float(cinv)))
 
+    def set_scaling_full(self, k, D, Dinv, E, Einv, c, cinv):
+        """set_scaling plus D, E, c themselves: the device update pass (apply_updates) scales with exactly these."""
+        self._chk(self.lib.cosmo_hip_batch_set_scaling_full(self._b, int(k), _dp(self._f(D, self.n)), _dp(self._f(Dinv, self.n)), _dp(self._f(E, self.m)),
+                                                            _dp(self._f(Einv, self.m)), float(c), float(cinv)))
+
     def set_params(self, params):
         self._chk(self.lib.cosmo_hip_batch_set_params(self._b, C.byref(params)))
+
+    def stage_qb(self, k, q=None, b=None):
+        """Stage the RAW (unscaled) q and / or b of member k for the next apply_updates (host only)."""
+        self._chk(self.lib.cosmo_hip_batch_stage_qb(self._b, int(k), _dp(self._f(q, self.n, "q")), _dp(self._f(b, self.m, "b"))))
+
+    def apply_updates(self):
+        """Every staged vector in one copy and one launch: scaled on the device, rows of Nonnegatives cones re-classified."""
+        self._chk(self.lib.cosmo_hip_batch_apply_updates(self._b))
+
+    def update_qb(self, members, q=None, b=None):
+        """stage_qb of len(members) members (q: len * n raw values or None, b: len * m or None), then apply_updates."""
+        mem = np.ascontiguousarray(members, dtype=np.int64)
+        self._chk(self.lib.cosmo_hip_batch_update_qb(self._b, mem.size, mem.ctypes.data_as(_PI64), _dp(self._f(q, mem.size * self.n, "q")),
+                                                     _dp(self._f(b, mem.size * self.m, "b"))))
+
+    def warm_restart(self):
+        """The next optimize starts from the batch's own final iterates (re-optimize: accelerator, status and counters restarted, rho kept)."""
+        self._chk(self.lib.cosmo_hip_batch_warm_restart(self._b))
+
+    def get_qb(self, k):
+        """(q, b) of member k as the device holds them (scaled)."""
+        q = np.empty(self.n, dtype=self.dtype); b = np.empty(self.m, dtype=self.dtype)
+        self._chk(self.lib.cosmo_hip_batch_get_qb(self._b, int(k), _dp(q), _dp(b)))
+        return q, b
 
     def set_accelerator(self, kind=ACCEL_ANDERSON, mem=15, min_mem=3, safeguard=True, safeguard_tol=2.0, start_iter=2, start_accuracy=None):
         """`_make_accelerator!` (src/setup.jl:10-16) for every problem of the batch; before set_params.  mem <= 16 in batch mode."""
@@ -837,6 +876,22 @@ class BatchGroup:
 
     def set_params(self, params):
         self._chk(self.lib.cosmo_hip_batch_group_set_params(self._g, C.byref(params)))
+
+    def stage_qb(self, k, q=None, b=None):
+        n, m = self.dims[int(k)]
+        self._chk(self.lib.cosmo_hip_batch_group_stage_qb(self._g, int(k), _dp(self._f(q, n, "q")), _dp(self._f(b, m, "b"))))
+
+    def apply_updates(self):
+        self._chk(self.lib.cosmo_hip_batch_group_apply_updates(self._g))
+
+    def warm_restart(self):
+        self._chk(self.lib.cosmo_hip_batch_group_warm_restart(self._g))
+
+    def get_qb(self, k):
+        n, m = self.dims[int(k)]
+        q = np.empty(n, dtype=self.dtype); b = np.empty(m, dtype=self.dtype)
+        self._chk(self.lib.cosmo_hip_batch_group_get_qb(self._g, int(k), _dp(q), _dp(b)))
+        return q, b
 
     def class_info(self, with_modes=False):
         """(number of structure classes, class index of every problem[, mode of every problem: 0 persistent batch kernel, 1 its own handle])"""

@@ -2206,6 +2206,54 @@ __global__ __launch_bounds__(COSMO_BS) void k_batch_set_w(BatchDev D, const real
   }
 }
 
+// ---- resident re-solves (cosmo_hip_batch_apply_updates / cosmo_hip_batch_warm_restart) ---------------------------------------------------------
+// update!(model; q, b) (src/interface.jl:187-211) of the staged members, one workgroup each: val holds the member's raw q (n) and b (m), flag bit 0 / 1
+// which of them apply.  q <- (D .* q) .* c and b <- E .* b in the operand order of the host formula; the rows of Nonnegatives cones whose b changed are
+// classified again (classify_constraints!, setup.jl:75-85: class 2 above the infinity threshold, else 0; the other classes do not depend on b).
+__global__ __launch_bounds__(256) void k_batch_update_qb(int n, int m, const int32_t* __restrict__ mem, const int32_t* __restrict__ flag,
+                                                         const real* __restrict__ val, const real* __restrict__ Dsc, const real* __restrict__ Esc,
+                                                         const real* __restrict__ csc, const unsigned char* __restrict__ nonneg, real big,
+                                                         real* __restrict__ q, real* __restrict__ b, int* __restrict__ cls) {
+  const int j = blockIdx.x, f = flag[j];
+  const long long k = mem[j];
+  const real* v = val + (long long)j * (n + m);
+  if (f & 1) {
+    const real c = csc[k];
+    for (int i = threadIdx.x; i < n; i += blockDim.x) q[k * n + i] = (Dsc[k * n + i] * v[i]) * c;
+  }
+  if (f & 2) {
+    for (int i = threadIdx.x; i < m; i += blockDim.x) {
+      const real bs = Esc[k * m + i] * v[n + i];
+      b[k * m + i] = bs;
+      if (nonneg[i]) cls[k * m + i] = bs > big ? 2 : 0;
+    }
+  }
+}
+
+// The next optimize! warm-starts from the batch's own final iterates: reverse_scaling! (src/scaling.jl:170-179) followed by scale_variables!
+// (src/scaling.jl:118-123) as the host does them between two solves, then w = [x; mu ./ rho + s] (solver.jl:128-129) as k_batch_set_w.
+__global__ __launch_bounds__(COSMO_BS) void k_batch_warm_restart(BatchDev D, const real* __restrict__ Dsc, const real* __restrict__ Esc,
+                                                                 const real* __restrict__ csc) {
+  const long long N = (long long)D.nprob * (D.n + D.m);
+  for (long long g = (long long)blockIdx.x * COSMO_BS + threadIdx.x; g < N; g += (long long)gridDim.x * COSMO_BS) {
+    const long long k = g / (D.n + D.m); const int i = (int)(g % (D.n + D.m));
+    real wv;
+    if (i < D.n) {
+      const long long r = k * D.n + i;
+      wv = D.Dinv[r] * (Dsc[r] * D.w_prev[g]);                            // x is the head of w_prev (src/types.jl:274)
+    } else {
+      const long long r = k * D.m + (i - D.n);
+      const real E = Esc[r], Einv = D.Einv[r];
+      const real sv = E * (Einv * D.s[r]);
+      const real mv = (Einv * ((E * D.mu[r]) * D.cinv[k])) * csc[k];
+      wv = (R(1.0) / D.rho[r]) * mv + sv;
+      D.s[r] = sv;
+    }
+    D.w[g] = wv;
+    D.w_prev[g] = wv;
+  }
+}
+
 // =====================================================================================================================
 // host side: C ABI of the batch mode
 // =====================================================================================================================
@@ -2238,6 +2286,12 @@ struct cosmo_hip_batch {
   std::vector<uint32_t> h_slA, h_slT; std::vector<real> h_pdiag; std::vector<unsigned char> h_pdiag_has;
   // direct KKT solver (cosmo_hip_batch_set_direct): the switch, the requested ordering (empty: default) and the plan built by set_params
   bool direct_on = false; std::vector<int64_t> direct_perm; BLdlPlan* ldl = nullptr;
+  // resident re-solves (cosmo_hip_batch_stage_qb / apply_updates / warm_restart): D, E, c themselves (set_scaling_full; else the reciprocals of the
+  // inverses), their device copies and the per-row Nonnegatives flag (uploaded by the first update); the staged raw vectors, one slot per member
+  std::vector<real> hD, hE, hc;
+  const real *d_D = nullptr, *d_E = nullptr, *d_c = nullptr; const unsigned char* d_nonneg = nullptr;
+  std::vector<int32_t> stg_slot, stg_mem, stg_flag; std::vector<real> stg_val;
+  unsigned char* d_stage = nullptr;
 };
 
 static int32_t bfail(cosmo_hip_batch* b, int32_t code, const char* fmt, ...) {
@@ -2279,6 +2333,7 @@ extern "C" int32_t cosmo_hip_batch_create(cosmo_hip_batch** out, int32_t device_
   b->hq.assign((size_t)nprob * n, 0.0); b->hb.assign((size_t)nprob * m, 0.0);
   b->have.assign(nprob, 0);
   b->hDinv.assign((size_t)nprob * n, 1.0); b->hEinv.assign((size_t)nprob * m, 1.0); b->hcinv.assign(nprob, 1.0);
+  b->hD.assign((size_t)nprob * n, 1.0); b->hE.assign((size_t)nprob * m, 1.0); b->hc.assign(nprob, 1.0);
   cosmo_hip_default_params(&b->prm);
   memset(&b->D, 0, sizeof b->D);
   *out = b;
@@ -2387,6 +2442,20 @@ extern "C" int32_t cosmo_hip_batch_set_scaling(cosmo_hip_batch* b, int64_t k, co
   if (Dinv) std::copy(Dinv, Dinv + b->n, b->hDinv.begin() + (size_t)k * b->n);
   if (Einv) std::copy(Einv, Einv + b->m, b->hEinv.begin() + (size_t)k * b->m);
   b->hcinv[k] = cinv;
+  // D, E, c for the device update pass (cosmo_hip_batch_apply_updates): reciprocals here, the caller's own values through set_scaling_full
+  if (Dinv) for (long long i = 0; i < b->n; ++i) b->hD[(size_t)k * b->n + i] = R(1.0) / Dinv[i];
+  if (Einv) for (long long i = 0; i < b->m; ++i) b->hE[(size_t)k * b->m + i] = R(1.0) / Einv[i];
+  b->hc[k] = (real)(1.0 / cinv);
+  return COSMO_HIP_OK;
+}
+
+extern "C" int32_t cosmo_hip_batch_set_scaling_full(cosmo_hip_batch* b, int64_t k, const real* D, const real* Dinv, const real* E, const real* Einv, double c,
+                                                    double cinv) {
+  const int32_t rc = cosmo_hip_batch_set_scaling(b, k, Dinv, Einv, cinv);
+  if (rc) return rc;
+  if (D) std::copy(D, D + b->n, b->hD.begin() + (size_t)k * b->n);
+  if (E) std::copy(E, E + b->m, b->hE.begin() + (size_t)k * b->m);
+  b->hc[k] = (real)c;
   return COSMO_HIP_OK;
 }
 
@@ -3091,9 +3160,12 @@ extern "C" int32_t cosmo_hip_batch_set_params(cosmo_hip_batch* b, const cosmo_hi
 
 extern "C" int32_t cosmo_hip_batch_get_rho_classes(cosmo_hip_batch* b, int64_t k, int32_t* cls) {
   if (!b || !b->finalized || k < 0 || k >= b->nprob || !cls) return bfail(b, COSMO_HIP_ERR_INVALID, "batch_get_rho_classes: bad call");
-  std::copy(b->cls_host.begin() + (size_t)k * b->m, b->cls_host.begin() + (size_t)(k + 1) * b->m, cls);
+  if (hipSetDevice(b->device) != hipSuccess) return bfail(b, COSMO_HIP_ERR_HIP, "hipSetDevice failed");
+  BHIP(b, hipMemcpy(cls, b->D.rho_cls + (size_t)k * b->m, (size_t)b->m * sizeof(int32_t), hipMemcpyDeviceToHost));     // (cosmo_hip_batch_apply_updates re-classifies there)
   return COSMO_HIP_OK;
 }
+
+static int32_t brestart_state(cosmo_hip_batch* b);
 
 // x0, s0, mu0: nprob*n, nprob*m, nprob*m (NULL = zeros)
 extern "C" int32_t cosmo_hip_batch_set_iterates(cosmo_hip_batch* b, const real* x0, const real* s0, const real* mu0) {
@@ -3107,7 +3179,11 @@ extern "C" int32_t cosmo_hip_batch_set_iterates(cosmo_hip_batch* b, const real* 
   hipLaunchKernelGGL(k_batch_set_w, dim3(2048), dim3(COSMO_BS), 0, b->stream, b->D, dx, ds, dm);
   BHIP(b, hipStreamSynchronize(b->stream));
   if (dx) (void)hipFree(dx); if (ds) (void)hipFree(ds); if (dm) (void)hipFree(dm);
-  // optimize! restarts at iter = 0 with status undetermined; KKT counters persist
+  return brestart_state(b);
+}
+
+// optimize! restarts at iter = 0 with status undetermined; KKT counters persist
+static int32_t brestart_state(cosmo_hip_batch* b) {
   std::vector<BCtl> c(b->nprob);
   BHIP(b, hipMemcpy(c.data(), b->D.ctl, sizeof(BCtl) * b->nprob, hipMemcpyDeviceToHost));
   for (auto& x : c) { x.status = 0; x.iter = 0; x.cost = INFINITY; x.r_prim = INFINITY; x.r_dual = INFINITY; x.max_norm_prim = 0; x.max_norm_dual = 0; }
@@ -3410,4 +3486,86 @@ extern "C" int32_t cosmo_hip_batch_direct_counts(cosmo_hip_batch* b, int64_t* ou
   if (!b->ldl) return bfail(b, COSMO_HIP_ERR_INVALID, "batch_direct_counts: the batch has no direct KKT solver (batch_set_direct, then set_params with kkt_kind DIRECT)");
   if (hipSetDevice(b->device) != hipSuccess) return bfail(b, COSMO_HIP_ERR_HIP, "hipSetDevice failed");
   return bldl_counts(b->ldl, b->D.ldl, b->stream, b->nprob, out, b->err);
+}
+
+// ---- resident re-solves: update!(model; q, b) on the device, then optimize! again (src/interface.jl:187-211, src/setup.jl:18-62) ----------------
+// The device copies of D, E, c and the per-row Nonnegatives flag, uploaded once (the first update or warm restart of the batch).
+static int32_t bresident_init(cosmo_hip_batch* b) {
+  if (b->d_D) return COSMO_HIP_OK;
+  int32_t rc;
+  std::vector<unsigned char> nn((size_t)b->m, 0);
+  for (size_t c = 0; c < b->cones.type.size(); ++c)
+    if (b->cones.type[c] == COSMO_HIP_NONNEG) for (long long i = 0; i < b->cones.dim[c]; ++i) nn[(size_t)(b->cones.off[c] + i)] = 1;
+  if ((rc = bup(b, &b->d_nonneg, nn)) || (rc = bup(b, &b->d_E, b->hE)) || (rc = bup(b, &b->d_c, b->hc))) return rc;
+  const size_t hdr = ((size_t)2 * b->nprob * sizeof(int32_t) + 15) / 16 * 16;
+  if ((rc = balloc(b, &b->d_stage, hdr + (size_t)b->nprob * (b->n + b->m) * sizeof(real)))) return rc;
+  b->stg_slot.assign((size_t)b->nprob, -1);
+  return bup(b, &b->d_D, b->hD);              // (last: d_D marks the set-up as done)
+}
+
+extern "C" int32_t cosmo_hip_batch_stage_qb(cosmo_hip_batch* b, int64_t k, const real* q, const real* bvec) {
+  if (!b || !b->finalized || k < 0 || k >= b->nprob) return bfail(b, COSMO_HIP_ERR_INVALID, "batch_stage_qb: bad call (set_params first; 0 <= k < nprob)");
+  if (!q && !bvec) return COSMO_HIP_OK;
+  if (hipSetDevice(b->device) != hipSuccess) return bfail(b, COSMO_HIP_ERR_HIP, "hipSetDevice failed");
+  { const int32_t rc = bresident_init(b); if (rc) return rc; }
+  const size_t N = (size_t)(b->n + b->m);
+  int32_t& slot = b->stg_slot[(size_t)k];
+  if (slot < 0) {
+    slot = (int32_t)b->stg_mem.size();
+    b->stg_mem.push_back((int32_t)k); b->stg_flag.push_back(0); b->stg_val.resize(b->stg_val.size() + N, R(0.0));
+  }
+  real* v = b->stg_val.data() + (size_t)slot * N;
+  if (q) { std::copy(q, q + b->n, v); b->stg_flag[(size_t)slot] |= 1; }
+  if (bvec) { std::copy(bvec, bvec + b->m, v + b->n); b->stg_flag[(size_t)slot] |= 2; }
+  return COSMO_HIP_OK;
+}
+
+extern "C" int32_t cosmo_hip_batch_apply_updates(cosmo_hip_batch* b) {
+  if (!b || !b->finalized) return bfail(b, COSMO_HIP_ERR_INVALID, "batch_apply_updates: set_params first");
+  const int cnt = (int)b->stg_mem.size();
+  if (cnt == 0) return COSMO_HIP_OK;
+  if (hipSetDevice(b->device) != hipSuccess) return bfail(b, COSMO_HIP_ERR_HIP, "hipSetDevice failed");
+  // one copy: {members, flags} (int32 each, padded to 16 bytes) followed by the n + m raw values of every staged member
+  const size_t N = (size_t)(b->n + b->m), hdr = ((size_t)2 * cnt * sizeof(int32_t) + 15) / 16 * 16, bytes = hdr + (size_t)cnt * N * sizeof(real);
+  std::vector<unsigned char> buf(bytes, 0);
+  memcpy(buf.data(), b->stg_mem.data(), (size_t)cnt * sizeof(int32_t));
+  memcpy(buf.data() + (size_t)cnt * sizeof(int32_t), b->stg_flag.data(), (size_t)cnt * sizeof(int32_t));
+  memcpy(buf.data() + hdr, b->stg_val.data(), (size_t)cnt * N * sizeof(real));
+  BHIP(b, hipMemcpyAsync(b->d_stage, buf.data(), bytes, hipMemcpyHostToDevice, b->stream));
+  const int32_t* dmem = reinterpret_cast<const int32_t*>(b->d_stage);
+  const real* dval = reinterpret_cast<const real*>(b->d_stage + hdr);
+  hipLaunchKernelGGL(k_batch_update_qb, dim3(cnt), dim3(256), 0, b->stream, (int)b->n, (int)b->m, dmem, dmem + cnt, dval, b->d_D, b->d_E, b->d_c,
+                     b->d_nonneg, (real)b->prm.cosmo_infty_min_scaling, const_cast<real*>(b->D.q), const_cast<real*>(b->D.b), const_cast<int*>(b->D.rho_cls));
+  BHIP(b, hipGetLastError());
+  BHIP(b, hipStreamSynchronize(b->stream));       // (buf is pageable host memory)
+  for (int32_t k : b->stg_mem) b->stg_slot[(size_t)k] = -1;
+  b->stg_mem.clear(); b->stg_flag.clear(); b->stg_val.clear();
+  return COSMO_HIP_OK;
+}
+
+extern "C" int32_t cosmo_hip_batch_update_qb(cosmo_hip_batch* b, int64_t count, const int64_t* members, const real* q, const real* bvec) {
+  if (!b || count < 0 || (count > 0 && !members)) return bfail(b, COSMO_HIP_ERR_INVALID, "batch_update_qb: bad arguments");
+  for (int64_t j = 0; j < count; ++j) {
+    const int32_t rc = cosmo_hip_batch_stage_qb(b, members[j], q ? q + (size_t)j * b->n : nullptr, bvec ? bvec + (size_t)j * b->m : nullptr);
+    if (rc) return rc;
+  }
+  return cosmo_hip_batch_apply_updates(b);
+}
+
+extern "C" int32_t cosmo_hip_batch_warm_restart(cosmo_hip_batch* b) {
+  if (!b || !b->have_iterates) return bfail(b, COSMO_HIP_ERR_INVALID, "batch_warm_restart: the batch has no iterates yet (set_iterates, optimize)");
+  if (hipSetDevice(b->device) != hipSuccess) return bfail(b, COSMO_HIP_ERR_HIP, "hipSetDevice failed");
+  { const int32_t rc = bresident_init(b); if (rc) return rc; }
+  hipLaunchKernelGGL(k_batch_warm_restart, dim3(2048), dim3(COSMO_BS), 0, b->stream, b->D, b->d_D, b->d_E, b->d_c);
+  BHIP(b, hipGetLastError());
+  BHIP(b, hipStreamSynchronize(b->stream));
+  return brestart_state(b);
+}
+
+extern "C" int32_t cosmo_hip_batch_get_qb(cosmo_hip_batch* b, int64_t k, real* q, real* bvec) {
+  if (!b || !b->finalized || k < 0 || k >= b->nprob) return bfail(b, COSMO_HIP_ERR_INVALID, "batch_get_qb: bad call");
+  if (hipSetDevice(b->device) != hipSuccess) return bfail(b, COSMO_HIP_ERR_HIP, "hipSetDevice failed");
+  if (q) BHIP(b, hipMemcpy(q, b->D.q + (size_t)k * b->n, (size_t)b->n * sizeof(real), hipMemcpyDeviceToHost));
+  if (bvec) BHIP(b, hipMemcpy(bvec, b->D.b + (size_t)k * b->m, (size_t)b->m * sizeof(real), hipMemcpyDeviceToHost));
+  return COSMO_HIP_OK;
 }

@@ -31,7 +31,9 @@ struct GProblem {
   std::vector<int64_t> Pp, Pi, Ap, Ai;
   std::vector<real> Px, Ax, q, b, box_l, box_u, Dinv, Einv, Dsc, Esc, x0, s0, mu0;     // Dsc / Esc: D, E themselves where the caller handed them over (set_scaling_full)
   std::vector<int32_t> ctype; std::vector<int64_t> cdim; std::vector<real> cparam;
-  double cinv = 1.0;
+  double cinv = 1.0, c = 0.0;     // c: set_scaling_full's (0: 1 / cinv)
+  std::vector<real> uq, ub;       // raw q / b staged for a member on its own handle (cosmo_hip_batch_group_stage_qb)
+  bool have_uq = false, have_ub = false;
   bool have = false, have_cones = false, have_scaling = false, have_x0 = false, have_s0 = false, have_mu0 = false;
   int cls = -1, pos = -1;         // class and position inside the class
   bool dirty = true;              // set_iterates was called for THIS problem since the class last ran (or it never ran)
@@ -144,8 +146,8 @@ extern "C" int32_t cosmo_hip_batch_group_set_scaling_full(cosmo_hip_batch_group*
                                                           double cinv) {
   const int32_t rc = cosmo_hip_batch_group_set_scaling(g, k, Dinv, Einv, cinv);
   if (rc) return rc;
-  (void)c;
   GProblem& p = g->prob[(size_t)k];
+  p.c = c;
   if (D) p.Dsc.assign(D, D + p.n); else p.Dsc.clear();
   if (E) p.Esc.assign(E, E + p.m); else p.Esc.clear();
   return COSMO_HIP_OK;
@@ -211,7 +213,11 @@ extern "C" int32_t cosmo_hip_batch_group_set_params(cosmo_hip_batch_group* g, co
       rc = cosmo_hip_batch_set_problem(C.b, (int64_t)j, p.Pp.data(), p.Pi.data(), p.Px.data(), p.Ap.data(), p.Ai.data(), p.Ax.data(), p.q.data(), p.b.data());
       if (rc) return bad(rc, "batch_set_problem");
       if (nbox) { std::copy(p.box_l.begin(), p.box_l.end(), bl.begin() + (size_t)(nbox * (long long)j)); std::copy(p.box_u.begin(), p.box_u.end(), bu.begin() + (size_t)(nbox * (long long)j)); }
-      if (p.have_scaling) { rc = cosmo_hip_batch_set_scaling(C.b, (int64_t)j, p.Dinv.data(), p.Einv.data(), p.cinv); if (rc) return bad(rc, "batch_set_scaling"); }
+      if (p.have_scaling) {
+        if (!p.Dsc.empty() && !p.Esc.empty()) rc = cosmo_hip_batch_set_scaling_full(C.b, (int64_t)j, p.Dsc.data(), p.Dinv.data(), p.Esc.data(), p.Einv.data(), p.c, p.cinv);
+        else rc = cosmo_hip_batch_set_scaling(C.b, (int64_t)j, p.Dinv.data(), p.Einv.data(), p.cinv);
+        if (rc) return bad(rc, "batch_set_scaling");
+      }
     }
     rc = cosmo_hip_batch_set_cones_ex(C.b, (int64_t)p0.ctype.size(), p0.ctype.data(), p0.cdim.data(), bl.data(), bu.data(), p0.cparam.data());
     if (rc == COSMO_HIP_OK && g->aa_on) rc = cosmo_hip_batch_set_accelerator(C.b, &g->aa);
@@ -462,4 +468,91 @@ extern "C" int32_t cosmo_hip_batch_group_get_accel_stats(cosmo_hip_batch_group* 
     for (size_t j = 0; j < C.members.size(); ++j) for (int t = 0; t < 6; ++t) out[6 * (size_t)C.members[j] + t] = c[6 * j + t];
   }
   return COSMO_HIP_OK;
+}
+
+// ---- resident re-solves (include/cosmo_hip.h: cosmo_hip_batch_group_stage_qb) -------------------------------------------------------------------------
+extern "C" int32_t cosmo_hip_batch_group_stage_qb(cosmo_hip_batch_group* g, int64_t k, const real* q, const real* bvec) {
+  GCHECK(g, k);
+  if (!g->finalized) return gfail(g, COSMO_HIP_ERR_INVALID, "batch_group_stage_qb: set_params first");
+  GProblem& p = g->prob[(size_t)k];
+  GClass& C = g->cls[(size_t)p.cls];
+  if (C.b) {
+    const int32_t rc = cosmo_hip_batch_stage_qb(C.b, p.pos, q, bvec);
+    return rc ? gfail(g, rc, std::string("batch_stage_qb: ") + cosmo_hip_batch_last_error(C.b)) : COSMO_HIP_OK;
+  }
+  if (q) { p.uq.assign(q, q + p.n); p.have_uq = true; }
+  if (bvec) { p.ub.assign(bvec, bvec + p.m); p.have_ub = true; }
+  return COSMO_HIP_OK;
+}
+
+// D, E, c of a problem: set_scaling_full's own values, else the reciprocals of the inverses (as cosmo_hip_set_scaling recovers them)
+static real gscale_D(const GProblem& p, long long i) { return p.Dsc.empty() ? R(1.0) / p.Dinv[(size_t)i] : p.Dsc[(size_t)i]; }
+static real gscale_E(const GProblem& p, long long i) { return p.Esc.empty() ? R(1.0) / p.Einv[(size_t)i] : p.Esc[(size_t)i]; }
+static real gscale_c(const GProblem& p) { return (real)(p.c != 0.0 ? p.c : 1.0 / p.cinv); }
+
+extern "C" int32_t cosmo_hip_batch_group_apply_updates(cosmo_hip_batch_group* g) {
+  if (!g || !g->finalized) return gfail(g, COSMO_HIP_ERR_INVALID, "batch_group_apply_updates: set_params first");
+  for (GClass& C : g->cls) {
+    if (C.b) {
+      const int32_t rc = cosmo_hip_batch_apply_updates(C.b);
+      if (rc) return gfail(g, rc, std::string("batch_apply_updates: ") + cosmo_hip_batch_last_error(C.b));
+      continue;
+    }
+    for (size_t j = 0; j < C.members.size(); ++j) {
+      GProblem& p = g->prob[(size_t)C.members[j]];
+      if (!p.have_uq && !p.have_ub) continue;
+      std::vector<real> qs, bs;                         // update! (src/interface.jl:196-208) with the scaled problem's D, E, c
+      if (p.have_uq) { qs.resize((size_t)p.n); const real c = p.have_scaling ? gscale_c(p) : R(1.0); for (long long i = 0; i < p.n; ++i) qs[(size_t)i] = p.have_scaling ? (gscale_D(p, i) * p.uq[(size_t)i]) * c : p.uq[(size_t)i]; }
+      if (p.have_ub) { bs.resize((size_t)p.m); for (long long i = 0; i < p.m; ++i) bs[(size_t)i] = p.have_scaling ? gscale_E(p, i) * p.ub[(size_t)i] : p.ub[(size_t)i]; }
+      const int32_t rc = cosmo_hip_update_qb(C.hs[j], p.have_uq ? qs.data() : nullptr, p.have_ub ? bs.data() : nullptr);
+      if (rc) return gfail(g, rc, std::string("update_qb of problem ") + std::to_string(C.members[j]) + ": " + cosmo_hip_last_error(C.hs[j]));
+      p.have_uq = p.have_ub = false;
+      std::vector<real>().swap(p.uq); std::vector<real>().swap(p.ub);
+    }
+  }
+  return COSMO_HIP_OK;
+}
+
+extern "C" int32_t cosmo_hip_batch_group_warm_restart(cosmo_hip_batch_group* g) {
+  if (!g || !g->finalized) return gfail(g, COSMO_HIP_ERR_INVALID, "batch_group_warm_restart: set_params first");
+  for (GClass& C : g->cls) {
+    if (!C.ran) return gfail(g, COSMO_HIP_ERR_INVALID, "batch_group_warm_restart: optimize the group first");
+    if (C.b) {
+      const int32_t rc = cosmo_hip_batch_warm_restart(C.b);
+      if (rc) return gfail(g, rc, std::string("batch_warm_restart: ") + cosmo_hip_batch_last_error(C.b));
+    } else {
+      for (size_t j = 0; j < C.members.size(); ++j) {
+        const GProblem& p = g->prob[(size_t)C.members[j]];
+        const long long n = p.n, m = p.m;
+        std::vector<real> w((size_t)(n + m)), wp((size_t)(n + m)), s((size_t)m), mu((size_t)m), x((size_t)n);
+        int32_t rc = cosmo_hip_get_iterates(C.hs[j], w.data(), wp.data(), s.data(), mu.data());
+        if (rc == COSMO_HIP_OK) {
+          // reverse_scaling! (src/scaling.jl:170-179) then scale_variables! (src/scaling.jl:118-123), as the host does them between two solves
+          const real c = p.have_scaling ? gscale_c(p) : R(1.0), cinv = p.have_scaling ? (real)p.cinv : R(1.0);
+          for (long long i = 0; i < n; ++i) { x[(size_t)i] = wp[(size_t)i]; if (p.have_scaling) x[(size_t)i] = p.Dinv[(size_t)i] * (gscale_D(p, i) * wp[(size_t)i]); }
+          if (p.have_scaling)
+            for (long long i = 0; i < m; ++i) {
+              const real E = gscale_E(p, i), Einv = p.Einv[(size_t)i];
+              s[(size_t)i] = E * (Einv * s[(size_t)i]);
+              mu[(size_t)i] = (Einv * ((E * mu[(size_t)i]) * cinv)) * c;
+            }
+          rc = cosmo_hip_set_iterates(C.hs[j], x.data(), s.data(), mu.data());
+        }
+        if (rc) return gfail(g, rc, std::string("warm restart of problem ") + std::to_string(C.members[j]) + ": " + cosmo_hip_last_error(C.hs[j]));
+      }
+    }
+    for (int k : C.members) g->prob[(size_t)k].dirty = false;
+    C.iterates_dirty = false;
+  }
+  return COSMO_HIP_OK;
+}
+
+extern "C" int32_t cosmo_hip_batch_group_get_qb(cosmo_hip_batch_group* g, int64_t k, real* q, real* bvec) {
+  GCHECK(g, k);
+  if (!g->finalized) return gfail(g, COSMO_HIP_ERR_INVALID, "batch_group_get_qb: set_params first");
+  const GProblem& p = g->prob[(size_t)k];
+  GClass& C = g->cls[(size_t)p.cls];
+  if (!C.b) return gfail(g, COSMO_HIP_ERR_UNSUPPORTED, "batch_group_get_qb: problem " + std::to_string(k) + " runs on its own handle");
+  const int32_t rc = cosmo_hip_batch_get_qb(C.b, p.pos, q, bvec);
+  return rc ? gfail(g, rc, cosmo_hip_batch_last_error(C.b)) : COSMO_HIP_OK;
 }

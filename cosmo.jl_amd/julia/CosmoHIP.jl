@@ -441,6 +441,49 @@ function batch_direct_counts(::Type{T}, b::Ptr{Cvoid}, nprob::Integer) where {T 
     return out
 end
 
+# Resident re-solves on a raw cosmo_hip_batch* `b` / cosmo_hip_batch_group* `g` of library T (include/cosmo_hip.h): update!(model; q, b) of members on
+# the device (raw, unscaled vectors; `nothing` leaves a vector alone), then optimize! again from the batch's own iterates.  batch_set_scaling_full!
+# goes before set_params (D, E, c themselves: the device scales with them); the others after it.  k is 0-based.
+function _rcheck(rc, what)
+    rc == 0 || error("$what failed (code $rc)")
+    return nothing
+end
+_rptr(v) = v === nothing ? C_NULL : pointer(v)
+function batch_set_scaling_full!(::Type{T}, b::Ptr{Cvoid}, k::Integer, D::Vector{T}, Dinv::Vector{T}, E::Vector{T}, Einv::Vector{T}, c::Real, cinv::Real) where {T <: HipFloat}
+    GC.@preserve D Dinv E Einv _rcheck(ccall((:cosmo_hip_batch_set_scaling_full, libpath(T)), Int32, (Ptr{Cvoid}, Int64, Ptr{T}, Ptr{T}, Ptr{T}, Ptr{T}, Cdouble, Cdouble),
+                                             b, Int64(k), D, Dinv, E, Einv, Float64(c), Float64(cinv)), "cosmo_hip_batch_set_scaling_full")
+end
+function batch_stage_qb!(::Type{T}, b::Ptr{Cvoid}, k::Integer, q::Union{Vector{T}, Nothing}, bvec::Union{Vector{T}, Nothing}) where {T <: HipFloat}
+    GC.@preserve q bvec _rcheck(ccall((:cosmo_hip_batch_stage_qb, libpath(T)), Int32, (Ptr{Cvoid}, Int64, Ptr{T}, Ptr{T}), b, Int64(k), _rptr(q), _rptr(bvec)),
+                                "cosmo_hip_batch_stage_qb")
+end
+batch_apply_updates!(::Type{T}, b::Ptr{Cvoid}) where {T <: HipFloat} =
+    _rcheck(ccall((:cosmo_hip_batch_apply_updates, libpath(T)), Int32, (Ptr{Cvoid},), b), "cosmo_hip_batch_apply_updates")
+function batch_update_qb!(::Type{T}, b::Ptr{Cvoid}, members::Vector{Int64}, q::Union{Vector{T}, Nothing}, bvec::Union{Vector{T}, Nothing}) where {T <: HipFloat}
+    GC.@preserve members q bvec _rcheck(ccall((:cosmo_hip_batch_update_qb, libpath(T)), Int32, (Ptr{Cvoid}, Int64, Ptr{Int64}, Ptr{T}, Ptr{T}),
+                                              b, Int64(length(members)), members, _rptr(q), _rptr(bvec)), "cosmo_hip_batch_update_qb")
+end
+batch_warm_restart!(::Type{T}, b::Ptr{Cvoid}) where {T <: HipFloat} =
+    _rcheck(ccall((:cosmo_hip_batch_warm_restart, libpath(T)), Int32, (Ptr{Cvoid},), b), "cosmo_hip_batch_warm_restart")
+function batch_get_qb(::Type{T}, b::Ptr{Cvoid}, k::Integer, n::Integer, m::Integer) where {T <: HipFloat}
+    q = zeros(T, n); bv = zeros(T, m)
+    _rcheck(ccall((:cosmo_hip_batch_get_qb, libpath(T)), Int32, (Ptr{Cvoid}, Int64, Ptr{T}, Ptr{T}), b, Int64(k), q, bv), "cosmo_hip_batch_get_qb")
+    return q, bv
+end
+function batch_group_stage_qb!(::Type{T}, g::Ptr{Cvoid}, k::Integer, q::Union{Vector{T}, Nothing}, bvec::Union{Vector{T}, Nothing}) where {T <: HipFloat}
+    GC.@preserve q bvec _rcheck(ccall((:cosmo_hip_batch_group_stage_qb, libpath(T)), Int32, (Ptr{Cvoid}, Int64, Ptr{T}, Ptr{T}), g, Int64(k), _rptr(q), _rptr(bvec)),
+                                "cosmo_hip_batch_group_stage_qb")
+end
+batch_group_apply_updates!(::Type{T}, g::Ptr{Cvoid}) where {T <: HipFloat} =
+    _rcheck(ccall((:cosmo_hip_batch_group_apply_updates, libpath(T)), Int32, (Ptr{Cvoid},), g), "cosmo_hip_batch_group_apply_updates")
+batch_group_warm_restart!(::Type{T}, g::Ptr{Cvoid}) where {T <: HipFloat} =
+    _rcheck(ccall((:cosmo_hip_batch_group_warm_restart, libpath(T)), Int32, (Ptr{Cvoid},), g), "cosmo_hip_batch_group_warm_restart")
+function batch_group_get_qb(::Type{T}, g::Ptr{Cvoid}, k::Integer, n::Integer, m::Integer) where {T <: HipFloat}
+    q = zeros(T, n); bv = zeros(T, m)
+    _rcheck(ccall((:cosmo_hip_batch_group_get_qb, libpath(T)), Int32, (Ptr{Cvoid}, Int64, Ptr{T}, Ptr{T}), g, Int64(k), q, bv), "cosmo_hip_batch_group_get_qb")
+    return q, bv
+end
+
 # direct_batch = true (with kkt_kind = KKT_DIRECT): every structure class runs the direct KKT solver inside its persistent batch kernel
 # (cosmo_hip_batch_group_set_direct) instead of one single-problem handle per member
 function optimize_hip_batch!(models::Vector{COSMO.Workspace{T}}; device::Integer = 0, kkt_kind::Int32 = KKT_CG, tol_constant = 1.0, tol_exponent = 1.5,

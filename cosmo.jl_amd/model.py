@@ -523,6 +523,7 @@ class Model:
         self.sm: Optional[ScaleMatrices] = None
         self.handle: Optional[_ffi.Handle] = None
         self.chordal = None            # _chordal.Decomposition of a decomposed model (ws.ci)
+        self.resident = None           # (BatchSolver, member index) while the model belongs to a resident batch
         self.x = self.s = self.mu = None
         self.n = self.m = 0
 
@@ -645,13 +646,22 @@ def update(model: Model, q=None, b=None):
         q = np.array(q, dtype=np.float64)
         if q.size != model.n:
             raise ValueError("The dimension of q, does not agree with the model dimension, n.")
-        model.q = (model.sm.D * q) * model.sm.c if model.is_scaled else q.copy()
+        if getattr(model, "chordal", None) is not None:
+            raise RuntimeError("Problem vector q can not be updated if the model has been chordally decomposed before.")
     if b is not None:
         b = np.array(b, dtype=np.float64)
         if b.size != model.m:
             raise ValueError("The dimension of b, does not agree with the model dimension, m.")
+        if getattr(model, "chordal", None) is not None:
+            raise RuntimeError("Problem vector b can not be updated if the model has been chordally decomposed before.")
+    if q is not None:
+        model.q = (model.sm.D * q) * model.sm.c if model.is_scaled else q.copy()
+    if b is not None:
         model.b = model.sm.E * b if model.is_scaled else b.copy()
-    if model.handle is not None:
+    rb = getattr(model, "resident", None)
+    if rb is not None:
+        rb[0]._stage(rb[1], q, b)                                 # a member of a BatchSolver: the raw vectors, scaled by the device update pass
+    elif model.handle is not None:
         model.handle.update_qb(model.q if q is not None else None, model.b if b is not None else None)
 
 
@@ -861,7 +871,7 @@ def shard_range(n_items: int, rank: int, world: int):
     return lo, lo + base + (1 if rank < rem else 0)
 
 
-def prepare_batch(models: Sequence[Model], device: int):
+def prepare_batch(models: Sequence[Model], device: int, scaling_full: bool = False):
     """setup! of every problem of a shard (host Ruiz scaling per problem, as the reference does per optimize! call) and upload
     into one `_ffi.Batch` (csrc/batch.hip), iterates set.  Returns (batch, settings actually used)."""
     if not models:
@@ -891,7 +901,10 @@ def prepare_batch(models: Sequence[Model], device: int):
             md.sm = ScaleMatrices(np.ones(n), np.ones(n), np.ones(m), np.ones(m), 1.0, 1.0)
         md.x = md.sm.Dinv * md.x; md.mu = (md.sm.Einv * md.mu) * md.sm.c; md.s = md.sm.E * md.s
         B.set_problem(k, md.P, md.q, md.A, md.b)
-        B.set_scaling(k, md.sm.Dinv, md.sm.Einv, md.sm.cinv)
+        if scaling_full:                                  # D, E, c themselves: BatchSolver's device update pass scales with them
+            B.set_scaling_full(k, md.sm.D, md.sm.Dinv, md.sm.E, md.sm.Einv, md.sm.c, md.sm.cinv)
+        else:
+            B.set_scaling(k, md.sm.Dinv, md.sm.Einv, md.sm.cinv)
         bl += [K.l for K in md.sets if K.kind == _ffi.BOX]; bu += [K.u for K in md.sets if K.kind == _ffi.BOX]
     B.set_cones(kinds, dims, np.concatenate(bl) if bl else None, np.concatenate(bu) if bu else None,
                 cone_param=[getattr(K, "alpha", 0.0) for K in models[0].sets])
@@ -1024,6 +1037,14 @@ def _solve_shard_on_device(models: Sequence[Model], device: int) -> List[Result]
     elif _direct_batch_of(st)[0]:
         LAST_BATCH_INFO["direct_info"] = B.direct_info()               # the LDL' form of the batch kernels ran (csrc/batch_ldl.hip)
         LAST_BATCH_INFO["direct_counts"] = B.direct_counts()
+    out = _write_back(models, B, rs, st, mixed, t0, t_setup)
+    B.close()
+    return out
+
+
+def _write_back(models, B, rs, st, mixed, t0, t_setup) -> List[Result]:
+    """The epilogue of optimize! (src/solver.jl:167-201) for every model of a batch: unscaled x, s, mu into the model, one Result each."""
+    import time
     out = []
     for k, (md, r) in enumerate(zip(models, rs)):
         w, w_prev, s, mu = B.get_iterates(k)
@@ -1041,8 +1062,99 @@ def _solve_shard_on_device(models: Sequence[Model], device: int) -> List[Result]
         out.append(Result(x=x, y=-mu, s=s, obj_val=r.cost, iter=int(r.iter), status=_ffi.STATUS_NAMES[r.status], info=info,
                           times=ResultTimes(time.perf_counter() - t0, t_setup, r.iter_time, 0.0), kkt_iters_total=int(r.kkt_iters_total),
                           safeguarding_iter=int(r.safeguarding_iter)))
-    B.close()
     return out
+
+
+class BatchSolver:
+    """A batch of models that stays on the MI355X across solves (the repeated-solve workloads: MPC, parameter sweeps, online re-solves).
+
+    The first `optimize()` sets the batch up as `optimize_batch` does (host Ruiz scaling, upload; a mixed list becomes a batch group) and keeps it.
+    `update(model, q=..., b=...)` on a member stages its raw vectors; the next `optimize()` applies all staged changes in one copy and one launch
+    (csrc/batch.hip: k_batch_update_qb) and re-solves with the reference's second `optimize!` (src/setup.jl:18-62): no re-scaling, every rho vector and
+    KKT factor kept, the accelerator restarted, status / iteration count / certificates / time limit fresh, and the iterates warm-started from the batch's
+    own final ones on the device (warm_start="device") or from the models' x, s, mu (warm_start="models", e.g. after warm_start_primal).
+    Results are written back to the models as `optimize_batch` does.  `close()` releases the device batch and unbinds the models."""
+
+    def __init__(self, models: Sequence[Model], device: Optional[int] = None, dist=None):
+        if dist is not None and dist.get_world_size() > 1:
+            raise NotImplementedError("BatchSolver: a resident batch is not sharded over torch.distributed ranks; use optimize_batch, or one BatchSolver "
+                                      "per rank on that rank's shard (shard_range)")
+        models = list(models)
+        if not models:
+            raise ValueError("BatchSolver: empty list of models")
+        for md in models:
+            if not md.is_assembled:
+                raise RuntimeError("The model has to be assembled! / set! before optimize!() can be called.")
+            if getattr(md, "resident", None) is not None:
+                raise ValueError("BatchSolver: a model belongs to at most one resident batch (close the other one first)")
+            if getattr(md, "chordal", None) is not None:
+                raise ValueError("BatchSolver: chordally decomposed models cannot be updated; solve them with optimize()")
+        if len({id(md) for md in models}) != len(models):
+            raise ValueError("BatchSolver: a model appears twice")
+        self.models = models
+        self.device = 0 if device is None else int(device)
+        self._B = None
+        self._st = None
+        self.mixed = None
+        self.last_times = {}                              # of the last optimize: first set-up, or the update pass and the warm restart (seconds)
+        for k, md in enumerate(models):
+            md.resident = (self, k)
+
+    def _stage(self, k, q, b):
+        if self._B is None:
+            return                                        # not on the device yet: the first optimize uploads the model's q / b
+        self._B.stage_qb(k, q, b)
+
+    def optimize(self, warm_start: str = "device") -> List[Result]:
+        import time
+        if warm_start not in ("device", "models"):
+            raise ValueError("BatchSolver.optimize: warm_start is 'device' or 'models'")
+        if self.models is None:
+            raise RuntimeError("BatchSolver: closed")
+        t0 = time.perf_counter()
+        models = self.models
+        if self._B is None:
+            _check_batch_psd_projection(models)
+            self.mixed = len({_structure_key(md) for md in models}) > 1 or not _batch_kernels_take(models[0])
+            self._B, self._st = prepare_batch_group(models, self.device) if self.mixed else prepare_batch(models, self.device, scaling_full=True)
+            self.last_times = dict(setup_s=time.perf_counter() - t0)
+        else:
+            B = self._B
+            B.apply_updates()                             # every staged q / b: one copy and one launch per batch
+            t1 = time.perf_counter()
+            if warm_start == "device":
+                B.warm_restart()
+            else:                                         # scale_variables! (src/scaling.jl:118-123) of the models' iterates, as setup! does
+                xs = [md.sm.Dinv * md.x for md in models]; ss = [md.sm.E * md.s for md in models]; ms = [(md.sm.Einv * md.mu) * md.sm.c for md in models]
+                if self.mixed:
+                    for k in range(len(models)):
+                        B.set_iterates(k, xs[k], ss[k], ms[k])
+                else:
+                    B.set_iterates(np.concatenate(xs), np.concatenate(ss), np.concatenate(ms))
+            self.last_times = dict(apply_s=t1 - t0, restart_s=time.perf_counter() - t1)
+        t_setup = time.perf_counter() - t0
+        rs = self._B.optimize()
+        return _write_back(models, self._B, rs, self._st, self.mixed, t0, t_setup)
+
+    @property
+    def batch(self):
+        """The device batch (`_ffi.Batch`, or `_ffi.BatchGroup` for a mixed list); None before the first optimize."""
+        return self._B
+
+    def close(self):
+        if self._B is not None:
+            self._B.close()
+            self._B = None
+        for md in self.models or []:
+            if getattr(md, "resident", None) is not None and md.resident[0] is self:
+                md.resident = None
+        self.models = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
 
 
 def optimize_batch(models: Sequence[Model], device: Optional[int] = None, dist=None, solve_shard=None) -> List[Result]:

@@ -530,6 +530,26 @@ COSMO_HIP_API int32_t cosmo_hip_batch_set_direct(cosmo_hip_batch* b, int32_t on,
 COSMO_HIP_API int32_t cosmo_hip_batch_direct_info(cosmo_hip_batch* b, int64_t out[8]);
 /* factorisations of every member so far (the set-up one included): out[nprob] */
 COSMO_HIP_API int32_t cosmo_hip_batch_direct_counts(cosmo_hip_batch* b, int64_t* out /* nprob */);
+/* Resident re-solves (update!(model; q, b), src/interface.jl:187-211, then optimize! again): the batch stays on the device between solves.
+ * cosmo_hip_batch_set_scaling_full: cosmo_hip_batch_set_scaling plus D, E, c themselves (before set_params); the device update scales with them, so the
+ *   scaled vectors are bit-identical to the host formula q <- (D .* q) .* c, b <- E .* b.  Without it the reciprocals of Dinv, Einv, cinv are used.
+ * cosmo_hip_batch_stage_qb: after set_params; stages the RAW (unscaled) q (n entries) and / or b (m entries) of member k on the host (NULL: that vector
+ *   is left alone; staging a member again overwrites).
+ * cosmo_hip_batch_apply_updates: every staged vector in one host-to-device copy of 8 * count + count * (n + m) * sizeof(cosmo_hip_real) bytes (header
+ *   padded to 16) and one launch: scales, writes the vectors the batch kernels read and re-classifies the Nonnegatives rows whose b changed
+ *   (classify_constraints!).  The rho vectors, the direct solver's factors and the iterates are left alone.
+ * cosmo_hip_batch_update_qb: stage `count` members (members: count indices; q: count * n or NULL; bvec: count * m or NULL) and apply.
+ * cosmo_hip_batch_warm_restart: the next cosmo_hip_batch_optimize starts from the batch's own final iterates (reverse_scaling! then scale_variables!,
+ *   on the device), with status, iteration count, certificates and the accelerator restarted and every rho kept (src/setup.jl:18-62); it replaces
+ *   cosmo_hip_batch_set_iterates, which stays available for caller-given iterates.
+ * cosmo_hip_batch_get_qb: the scaled q (n) and / or b (m) of member k as the device holds them (NULL: skip). */
+COSMO_HIP_API int32_t cosmo_hip_batch_set_scaling_full(cosmo_hip_batch* b, int64_t k, const cosmo_hip_real* D, const cosmo_hip_real* Dinv, const cosmo_hip_real* E,
+                                                       const cosmo_hip_real* Einv, double c, double cinv);
+COSMO_HIP_API int32_t cosmo_hip_batch_stage_qb(cosmo_hip_batch* b, int64_t k, const cosmo_hip_real* q /* n or NULL */, const cosmo_hip_real* bvec /* m or NULL */);
+COSMO_HIP_API int32_t cosmo_hip_batch_apply_updates(cosmo_hip_batch* b);
+COSMO_HIP_API int32_t cosmo_hip_batch_update_qb(cosmo_hip_batch* b, int64_t count, const int64_t* members, const cosmo_hip_real* q, const cosmo_hip_real* bvec);
+COSMO_HIP_API int32_t cosmo_hip_batch_warm_restart(cosmo_hip_batch* b);
+COSMO_HIP_API int32_t cosmo_hip_batch_get_qb(cosmo_hip_batch* b, int64_t k, cosmo_hip_real* q /* n or NULL */, cosmo_hip_real* bvec /* m or NULL */);
 
 /* ---- batches of problems of DIFFERENT structure (csrc/batch_group.hip) ------------------------------------------------------------------
  * The reference's batch is a loop over arbitrary models (src/solver.jl:78).  A group takes every problem with ITS OWN (n, m, cones), partitions
@@ -576,6 +596,15 @@ COSMO_HIP_API int32_t cosmo_hip_batch_group_optimize(cosmo_hip_batch_group* g, c
 COSMO_HIP_API int32_t cosmo_hip_batch_group_get_iterates(cosmo_hip_batch_group* g, int64_t k, cosmo_hip_real* w, cosmo_hip_real* w_prev, cosmo_hip_real* s, cosmo_hip_real* mu);
 COSMO_HIP_API int32_t cosmo_hip_batch_group_get_counters(cosmo_hip_batch_group* g, int64_t* out /* 3 * nprob */);
 COSMO_HIP_API int32_t cosmo_hip_batch_group_get_accel_stats(cosmo_hip_batch_group* g, int64_t* out /* 6 * nprob */);
+/* Resident re-solves of a group (see cosmo_hip_batch_stage_qb): after set_params.  stage_qb stages the raw q (n_k) / b (m_k) of problem k; apply_updates
+ * applies every staged vector: one copy and one launch per class batch, cosmo_hip_update_qb (scaled on the host with D, E, c) for members on their own
+ * handles.  warm_restart makes the next cosmo_hip_batch_group_optimize start every problem from its own final iterates (cosmo_hip_batch_warm_restart per
+ * class batch; reverse_scaling! + scale_variables! on the host and cosmo_hip_set_iterates for members on their own handles).  get_qb reads the scaled
+ * vectors of a member of a class batch (UNSUPPORTED for a member on its own handle). */
+COSMO_HIP_API int32_t cosmo_hip_batch_group_stage_qb(cosmo_hip_batch_group* g, int64_t k, const cosmo_hip_real* q, const cosmo_hip_real* bvec);
+COSMO_HIP_API int32_t cosmo_hip_batch_group_apply_updates(cosmo_hip_batch_group* g);
+COSMO_HIP_API int32_t cosmo_hip_batch_group_warm_restart(cosmo_hip_batch_group* g);
+COSMO_HIP_API int32_t cosmo_hip_batch_group_get_qb(cosmo_hip_batch_group* g, int64_t k, cosmo_hip_real* q, cosmo_hip_real* bvec);
 
 #ifdef __cplusplus
 }
