@@ -3,7 +3,10 @@
   * one solve! against a dense solve of the same quasi-definite system (the reference's bars, test/UnitTests/kktsolver.jl:40), after update_rho!
     with a non-uniform rho, and bitwise repeatability;
   * whole solves against the NumPy oracle's direct path (kkt_solver="qdldl": exact LDL' solves, refactorised at every rho update);
-  * the inertia check ("Objective function is not convex."), the refusal of row sharding, the Float32 library."""
+  * the inertia check ("Objective function is not convex."), the refusal of row sharding, the Float32 library.
+
+Structural coverage (supernodes wider / taller than the workgroup, thousands of descendants or levels, N > 4096 * 256, missing diagonals, P = 0,
+m = 0, empty lines) against a derived backward-error bound: tests/test_gpu_ldl_structures.py."""
 import numpy as np
 import pytest
 import scipy.sparse as sp
