@@ -778,7 +778,10 @@ class Batch:
         return list(res)
 
     def iterate(self, n_iters, with_init=False):
-        """n_iters more loop bodies of every undecided problem (residual / adaptive-rho checks on schedule).  The infeasibility certificates
+        """n_iters more loop bodies of every undecided problem (residual / adaptive-rho checks on schedule).  A loop body starts with admm_z
+        (w_prev = w, then s = Pi(w_s), solver.jl:151-152) and ends with the KKT solve and the update of w, which never writes s: after iterate(1)
+        get_iterates returns in w_prev[n:] the exact input of the cone projection and in s its result (tests/test_gpu_batch_projections.py relies
+        on this order).  with_init runs one KKT solve and update in front of the first body (solver.jl:137-138).  The infeasibility certificates
         are NOT evaluated here -- only optimize() cuts the persistent launch for them -- so rates measured through iterate() exclude their cost."""
         self._chk(self.lib.cosmo_hip_batch_iterate(self._b, int(n_iters), 1 if with_init else 0))
 

@@ -122,7 +122,10 @@ __device__ __forceinline__ real proj_simple(real x, uint32_t meta, const real* b
 // ---------------------------------------------------------------------------------------------------------------------
 // Two ways of applying a problem's matrices inside its workgroup; both give every row to one thread that adds the row's
 // products left to right (the order of Julia's CSC kernels), and both visit the rows in the order of the same tile
-// descriptors, so per-thread accumulations and therefore all results are bit-identical between them.
+// descriptors, so per-thread accumulations and therefore all results are bit-identical between them -- with one exception: a PSD cone of side
+// 17 .. 64 is shifted by ||X||_F, which psdwg_populate<BS> sums over BS-strided elements and BS / 64 wave partials, and the streaming kernel has
+// 256 threads where the LDS-image kernel has 512.  The two projections of such a cone agree to rounding (64 d eps ||X||_F, both against eigh:
+// tests/test_gpu_batch_projections.py), not to the bit.
 //   StreamOps : values / indices stream from global memory tile by tile through a 16 KB LDS product buffer (any size).
 //   LdsOps    : the whole problem is copied ONCE per launch into the workgroup's LDS -- A as (fp64 value, u16 column),
 //               A' as (u16 position into A's values, u16 row) so the values are held once, P, the tile descriptors and

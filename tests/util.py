@@ -38,6 +38,23 @@ def model_sets(cones):
     return out
 
 
+def projection_sets(cones):
+    """the model sets of a cone list of tests/projection_cases.py"""
+    from tests import projection_cases as S
+    plain = {S.ZERO: cj.ZeroSet, S.NONNEG: cj.Nonnegatives, S.SOC: cj.SecondOrderCone, S.PSD_SQ: cj.PsdCone, S.PSD_TRI: cj.PsdConeTriangle}
+    out = []
+    for c in cones:
+        if c.kind == S.BOX:
+            out.append(cj.Box(c.l, c.u))
+        elif c.kind in (S.EXP, S.DUAL_EXP):
+            out.append((cj.ExponentialCone if c.kind == S.EXP else cj.DualExponentialCone)())
+        elif c.kind in (S.POW, S.DUAL_POW):
+            out.append((cj.PowerCone if c.kind == S.POW else cj.DualPowerCone)(c.alpha))
+        else:
+            out.append(plain[c.kind](c.dim))
+    return out
+
+
 def oracle_settings(**kw):
     return O.Settings(**kw)
 
