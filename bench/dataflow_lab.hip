@@ -6,6 +6,9 @@
 //     reads the operands with sc1 loads (L1 bypass, served by the XCD's L2 -- the coherence point of producer and consumer, which sit in the same XCD by
 //     construction).  First version of this lab used plain loads behind `buffer_inv sc0`: WRONG (sc0 is a workgroup-scope invalidate with no effect on
 //     the L1; stale reads as soon as a CU re-reads a small region it has cached -- variant `inv0` below keeps that form to show it);
+//     operand loads = 2: the hand-off read by DIRECT-TO-LDS buffer loads (16 bytes per lane, one wave instruction = 1 KB of lane-linear LDS) carrying the same sc1
+//     bit, then checked out of LDS -- the question an LDS-DMA operand ring for k_polar_dataflow has to have answered first: does a load that never passes through
+//     a VGPR honour the cache policy of the register form, on buffers that are rewritten 44 times per launch and reused by every repetition?
 //   * tile body: read the cone's whole region (must hold the value p everywhere), spin `work` clocks, write the tile's slice with p + 1.
 // Reports: wall time of the persistent launch vs. 44 launches of the same tiles, stale reads, timeouts, workgroups per XCD.
 //   hipcc --offload-arch=gfx950 -O3 bench/dataflow_lab.hip -o bench/dataflow_lab
@@ -42,6 +45,20 @@ __device__ __forceinline__ void tile_body2(const Tile& td, double* buf, int p, u
   double* rd = buf + 2 * td.off + (size_t)(p & 1) * td.elems;
   double* wr = buf + 2 * td.off + (size_t)((p + 1) & 1) * td.elems;
   double acc = 0.0;
+  if constexpr (SC1 == 2) {
+    // elems is a multiple of 256 doubles, i.e. of 2 KB: every step of the workgroup moves 4 KB (256 lanes x 16 bytes), a last half step is done by waves 0-1 alone.
+    // LDS image of a step: wave w at byte 1024 w, lane l at + 16 l (the DMA's own lane-linear layout); no register holds the data on the way.
+    __shared__ double s_dma[512];
+    __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void*)rd, 0, td.elems * (int)sizeof(double), 0x00020000);
+    const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
+    for (int e0 = 0; e0 < td.elems; e0 += 512) {
+      const bool on = e0 + 128 * wv < td.elems;            // wave-uniform
+      if (on) __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (__attribute__((address_space(3))) void*)(s_dma + 128 * wv), 16, (e0 + 128 * wv) * 8 + 16 * lane, 0, 0, 16 /* sc1 */);
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      if (on) { const double v0 = s_dma[128 * wv + 2 * lane], v1 = s_dma[128 * wv + 2 * lane + 1]; acc += (v0 - p) * (v0 - p) + (v1 - p) * (v1 - p); }
+      __syncthreads();                                     // (each wave reads only what it loaded itself; the barrier keeps the steps of the workgroup together as a panel loop would)
+    }
+  } else
   for (int i = threadIdx.x; i < td.elems; i += 256) { const double v = SC1 ? __hip_atomic_load(rd + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : rd[i]; acc += (v - p) * (v - p); }
   for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
   if ((threadIdx.x & 63) == 0 && acc != 0.0) atomicAdd(stale, 1ull);
@@ -152,7 +169,7 @@ int main(int argc, char** argv) {
   Tile nul; nul.cone = -1;
   std::vector<Tile> il(8 * maxlen, nul);
   for (int x = 0; x < 8; ++x) for (size_t s = 0; s < xl[x].size(); ++s) il[8 * s + x] = xl[x][s];
-  printf("tiles %zu (per XCD:", dl.size()); for (int x = 0; x < 8; ++x) printf(" %zu", xl[x].size()); printf("), products %d, work %d clocks, persistent grid %d, cones %d, operand loads %s\n", nprod, work, grid, ncones, sc1 ? "sc1 (L1 bypass)" : "plain behind buffer_inv sc0 (WRONG form)");
+  printf("tiles %zu (per XCD:", dl.size()); for (int x = 0; x < 8; ++x) printf(" %zu", xl[x].size()); printf("), products %d, work %d clocks, persistent grid %d, cones %d, operand loads %s\n", nprod, work, grid, ncones, sc1 == 2 ? "sc1 direct-to-LDS (16 bytes per lane)" : sc1 ? "sc1 (L1 bypass)" : "plain behind buffer_inv sc0 (WRONG form)");
   Tile *d_dl, *d_il; int *d_nt, *d_xoff; unsigned *d_sync, *d_wg; double* d_buf; unsigned long long* d_stale;
   hipMalloc(&d_dl, sizeof(Tile) * dl.size()); hipMemcpy(d_dl, dl.data(), sizeof(Tile) * dl.size(), hipMemcpyHostToDevice);
   hipMalloc(&d_il, sizeof(Tile) * il.size()); hipMemcpy(d_il, il.data(), sizeof(Tile) * il.size(), hipMemcpyHostToDevice);
@@ -168,7 +185,8 @@ int main(int argc, char** argv) {
     hipMemset(d_sync, 0, sizeof(unsigned) * (SYNC_DONE + ncones));
     hipDeviceSynchronize();
     hipEventRecord(e0, 0);
-    if (sc1) hipLaunchKernelGGL(k_dataflow<1>, dim3(grid), dim3(256), 0, 0, d_dl, d_nt, d_sync, d_buf, nprod, d_xoff, d_stale, d_wg);
+    if (sc1 == 2) hipLaunchKernelGGL(k_dataflow<2>, dim3(grid), dim3(256), 0, 0, d_dl, d_nt, d_sync, d_buf, nprod, d_xoff, d_stale, d_wg);
+    else if (sc1) hipLaunchKernelGGL(k_dataflow<1>, dim3(grid), dim3(256), 0, 0, d_dl, d_nt, d_sync, d_buf, nprod, d_xoff, d_stale, d_wg);
     else hipLaunchKernelGGL(k_dataflow<0>, dim3(grid), dim3(256), 0, 0, d_dl, d_nt, d_sync, d_buf, nprod, d_xoff, d_stale, d_wg);
     hipEventRecord(e1, 0); hipEventSynchronize(e1); hipEventElapsedTime(&ms, e0, e1);
     unsigned long long st = 0; unsigned wg[8], sy[160];

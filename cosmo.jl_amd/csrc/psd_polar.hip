@@ -747,7 +747,15 @@ __device__ __forceinline__ real2 polar_ld_pair_sc1(__amdgpu_buffer_rsrc_t rs, in
   return make_real2(__hiloint2double((int)v[1], (int)v[0]), __hiloint2double((int)v[3], (int)v[2]));
 #endif
 }
-template <int NSL, int DEPTH, bool SC1, class PreLast>
+// Main loop of one ragged tile: acc[slot] += A(k-panel, block row)' B(k-panel, block column) over nk panels of PK = 16 rows of k.
+// Pipeline: register-staged LDS double buffer.  The 64-wide panels of step kb + 1 (DEPTH = 2: also kb + 2) are requested into registers before the matrix
+// instructions of panel kb, written to the other LDS buffer after them, one workgroup barrier per panel; the last panel is peeled (pre_last hook).
+// SAME: the two operands are the same panel -- a diagonal tile of a square product (ia == ib, i0 == j0; Y = U^2 and Y^2 are 30 of BASELINE config 5's 47
+// products), where the two-panel form loads, stores and holds the same bytes twice: 17 % of the operand loads of that schedule.  Only the A panel is loaded and
+// written to LDS and the B fragments are read from the A panel's image: the same values reach every matrix instruction in the same order, hence the same bits.
+// SAME is decided per tile before the loop (ragged_tile: offA == offB, workgroup-uniform) and is a template parameter, not a branch inside the loop (as a
+// branch it cost the persistent kernel 9 more spilled registers): the single-panel form holds half the staging registers, the two-panel form is the code it was.
+template <int NSL, int DEPTH, bool SC1, bool SAME, class PreLast>
 __device__ __forceinline__ void symm_mainloop_r(const real* __restrict__ A, const real* __restrict__ B, int ld, int i0, int j0, int nk, real* smem,
                                                 v4d (&acc)[4], const int (&oa)[4], const int (&ob)[4], PreLast pre_last, __amdgpu_buffer_rsrc_t rs, int offA, int offB
 #ifdef POLAR_LAB_TIMING
@@ -758,29 +766,34 @@ __device__ __forceinline__ void symm_mainloop_r(const real* __restrict__ A, cons
   constexpr int NL = Cfg::NL, PITCH = Cfg::PITCH, PANEL = Cfg::PANEL;
   real* As = smem;
   real* Bs = As + 2 * PANEL;
-  const int lane = threadIdx.x & 63;
+  // The thread index goes through an empty asm: in the persistent kernel the per-thread offsets below are loop invariants of the TILE loop, and hoisted out
+  // of it they were what the full register file spilled (12 bytes of scratch per lane, reloaded in every tile).  Recomputed per tile they cost a few integer
+  // instructions and no register outside the main loop.
+  int tid = (int)threadIdx.x;
+  asm volatile("" : "+v"(tid));
+  const int lane = tid & 63;
   const long long pstep = (long long)PK * ld;
   int goff[NL], soff[NL];
 #pragma unroll
   for (int u = 0; u < NL; ++u) {
-    const int q = threadIdx.x + 256 * u;
+    const int q = tid + 256 * u;
     const int k = q / 32, c2 = q % 32;
     goff[u] = k * ld + 2 * c2;
     soff[u] = k * PITCH + 2 * c2;
   }
   const real* ga = A + i0;
   const real* gb = B + j0;
-  real2 r[DEPTH][2 * NL];          // DEPTH = 2: panels kb + 1 and kb + 2 in flight; DEPTH = 1 (the four-waves-per-SIMD build): panel kb + 1 only
+  real2 r[DEPTH][SAME ? NL : 2 * NL];          // DEPTH = 2: panels kb + 1 and kb + 2 in flight; DEPTH = 1 (the four-waves-per-SIMD build): panel kb + 1 only
 #define R_LOAD(R, KB)                                                                                     \
   {                                                                                                       \
     const long long o_ = (long long)(KB) * pstep;                                                         \
     _Pragma("unroll") for (int u = 0; u < NL; ++u) {                                                      \
       if constexpr (SC1) {                                                                                \
         (R)[u] = polar_ld_pair_sc1(rs, (offA + (int)o_ + goff[u]) * (int)sizeof(real));                   \
-        (R)[NL + u] = polar_ld_pair_sc1(rs, (offB + (int)o_ + goff[u]) * (int)sizeof(real));              \
+        if constexpr (!SAME) (R)[NL + u] = polar_ld_pair_sc1(rs, (offB + (int)o_ + goff[u]) * (int)sizeof(real)); \
       } else {                                                                                            \
         (R)[u] = *reinterpret_cast<const real2*>(ga + o_ + goff[u]);                                      \
-        (R)[NL + u] = *reinterpret_cast<const real2*>(gb + o_ + goff[u]);                                 \
+        if constexpr (!SAME) (R)[NL + u] = *reinterpret_cast<const real2*>(gb + o_ + goff[u]);            \
       }                                                                                                   \
     }                                                                                                     \
   }
@@ -790,13 +803,13 @@ __device__ __forceinline__ void symm_mainloop_r(const real* __restrict__ A, cons
       real* pa_ = As + (BUF) * PANEL + soff[u];                                                           \
       real* pb_ = Bs + (BUF) * PANEL + soff[u];                                                           \
       pa_[0] = (R)[u].x; pa_[1] = (R)[u].y;                                                               \
-      pb_[0] = (R)[NL + u].x; pb_[1] = (R)[NL + u].y;                                                     \
+      if constexpr (!SAME) { pb_[0] = (R)[NL + u].x; pb_[1] = (R)[NL + u].y; }                            \
     }                                                                                                     \
   }
   const int fl = lane & 15, fk = lane >> 4;
   const real* apb[4]; const real* bpb[4];
 #pragma unroll
-  for (int sl = 0; sl < 4; ++sl) { apb[sl] = As + fk * PITCH + fl + oa[sl]; bpb[sl] = Bs + fk * PITCH + fl + ob[sl]; }
+  for (int sl = 0; sl < 4; ++sl) { apb[sl] = As + fk * PITCH + fl + oa[sl]; bpb[sl] = (SAME ? As : Bs) + fk * PITCH + fl + ob[sl]; }
 #define R_COMPUTE(BUF)                                                                                    \
   {                                                                                                       \
     _Pragma("unroll") for (int ks = 0; ks < PK / 4; ++ks) {                                               \
@@ -900,13 +913,25 @@ __device__ __forceinline__ void ragged_tile(const RTile& td, real* __restrict__ 
   __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void*)base, 0, SC1 ? (int)(4 * n2 * (long long)sizeof(real)) : 0, 0x00020000);
   const int offA = (int)(ia * n2) + td.i0, offB = (int)(ib * n2) + td.j0;
 #ifndef POLAR_LAB_NO_MAINLOOP               // lab builds (tools/build_lab_variants.sh): epilogue only / main loop only
+#define R_MAINLOOP(NSL_, SAME_) symm_mainloop_r<NSL_, (OCC >= 4 ? 1 : 2), SC1, SAME_>(A, B, ld, i0, j0, nk, smem, acc, oa, ob, pre_last, rs, offA, offB RT_ARG)
+#ifndef POLAR_LAB_TWO_PANELS               // lab build (tools/build_lab_variants.sh TWO_PANELS): every tile loads both panels -- what the single-panel form is measured against
+  if (diag && offA == offB) {                // workgroup-uniform: the two operands are the same panel (diagonal tile of a square product: at most 10 blocks, 3 per wave)
+    switch (nsl) {
+      case 3: R_MAINLOOP(3, true); break;
+      case 2: R_MAINLOOP(2, true); break;
+      case 1: R_MAINLOOP(1, true); break;
+      default: R_MAINLOOP(0, true); break;
+    }
+  } else
+#endif
   switch (nsl) {                             // wave-uniform; a wave without a block still takes part in the panel loads and barriers
-    case 4: symm_mainloop_r<4, (OCC >= 4 ? 1 : 2), SC1>(A, B, ld, i0, j0, nk, smem, acc, oa, ob, pre_last, rs, offA, offB RT_ARG); break;
-    case 3: symm_mainloop_r<3, (OCC >= 4 ? 1 : 2), SC1>(A, B, ld, i0, j0, nk, smem, acc, oa, ob, pre_last, rs, offA, offB RT_ARG); break;
-    case 2: symm_mainloop_r<2, (OCC >= 4 ? 1 : 2), SC1>(A, B, ld, i0, j0, nk, smem, acc, oa, ob, pre_last, rs, offA, offB RT_ARG); break;
-    case 1: symm_mainloop_r<1, (OCC >= 4 ? 1 : 2), SC1>(A, B, ld, i0, j0, nk, smem, acc, oa, ob, pre_last, rs, offA, offB RT_ARG); break;
-    default: symm_mainloop_r<0, (OCC >= 4 ? 1 : 2), SC1>(A, B, ld, i0, j0, nk, smem, acc, oa, ob, pre_last, rs, offA, offB RT_ARG); break;
+    case 4: R_MAINLOOP(4, false); break;
+    case 3: R_MAINLOOP(3, false); break;
+    case 2: R_MAINLOOP(2, false); break;
+    case 1: R_MAINLOOP(1, false); break;
+    default: R_MAINLOOP(0, false); break;
   }
+#undef R_MAINLOOP
 #else
   (void)A; (void)B; (void)nk; (void)pre_last;
 #endif
