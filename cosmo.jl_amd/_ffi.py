@@ -159,6 +159,10 @@ SIGNATURES = {
     "cosmo_hip_batch_update_qb": (C.c_int32, [C.c_void_p, C.c_int64, _PI64, _PR, _PR]),
     "cosmo_hip_batch_warm_restart": (C.c_int32, [C.c_void_p]),
     "cosmo_hip_batch_get_qb": (C.c_int32, [C.c_void_p, C.c_int64, _PR, _PR]),
+    "cosmo_hip_batch_scale_ruiz": (C.c_int32, [C.c_void_p, C.c_int64, C.c_double, C.c_double]),
+    "cosmo_hip_batch_get_scaling": (C.c_int32, [C.c_void_p, C.c_int64, _PR, _PR, _PD]),
+    "cosmo_hip_batch_get_scaled_problem": (C.c_int32, [C.c_void_p, C.c_int64, _PR, _PR, _PR, _PR, _PR, _PR]),
+    "cosmo_hip_batch_ruiz_info": (C.c_int32, [C.c_void_p, _PI64]),
     "cosmo_hip_batch_group_create": (C.c_int32, [C.POINTER(C.c_void_p), C.c_int32, C.c_int64]),
     "cosmo_hip_batch_group_destroy": (C.c_int32, [C.c_void_p]),
     "cosmo_hip_batch_group_last_error": (C.c_char_p, [C.c_void_p]),
@@ -168,6 +172,8 @@ SIGNATURES = {
     "cosmo_hip_batch_group_set_scaling_full": (C.c_int32, [C.c_void_p, C.c_int64, _PR, _PR, _PR, _PR, C.c_double, C.c_double]),
     "cosmo_hip_batch_group_set_accelerator": (C.c_int32, [C.c_void_p, C.POINTER(AccelParams)]),
     "cosmo_hip_batch_group_set_direct": (C.c_int32, [C.c_void_p, C.c_int32]),
+    "cosmo_hip_batch_group_set_device_scaling": (C.c_int32, [C.c_void_p, C.c_int64, C.c_double, C.c_double]),
+    "cosmo_hip_batch_group_get_scaling": (C.c_int32, [C.c_void_p, C.c_int64, _PR, _PR, _PD]),
     "cosmo_hip_batch_group_set_params": (C.c_int32, [C.c_void_p, C.POINTER(Params)]),
     "cosmo_hip_batch_group_class_info": (C.c_int32, [C.c_void_p, _PI64, _PI64, _PI64]),
     "cosmo_hip_batch_group_run_info": (C.c_int32, [C.c_void_p, _PI64]),
@@ -698,6 +704,32 @@ class Batch:
     def set_params(self, params):
         self._chk(self.lib.cosmo_hip_batch_set_params(self._b, C.byref(params)))
 
+    def scale_ruiz(self, iterations, min_scaling=1e-4, max_scaling=1e4):
+        """Device Ruiz equilibration of every staged member in one launch (csrc/batch_ruiz.hip); after set_problem / set_cones, before set_params,
+        instead of set_scaling*.  Read D, E, c with get_scaling."""
+        self._chk(self.lib.cosmo_hip_batch_scale_ruiz(self._b, int(iterations), float(min_scaling), float(max_scaling)))
+
+    def get_scaling(self, k):
+        """(D, E, c) of member k as the batch holds them."""
+        D = np.empty(self.n, dtype=self.dtype); E = np.empty(self.m, dtype=self.dtype); c = C.c_double(1.0)
+        self._chk(self.lib.cosmo_hip_batch_get_scaling(self._b, int(k), _dp(D), _dp(E), C.byref(c)))
+        return D, E, float(c.value)
+
+    def get_scaled_problem(self, k, nnzP, nnzA, nbox=0):
+        """The staged problem of member k (before set_params): (values of P row by row, values of A in CSC order, q, b, box_l, box_u).  Raises if the
+        member's three staged copies of A differ in a bit."""
+        Pv = np.empty(int(nnzP), dtype=self.dtype); Av = np.empty(int(nnzA), dtype=self.dtype)
+        q = np.empty(self.n, dtype=self.dtype); b = np.empty(self.m, dtype=self.dtype)
+        bl = np.empty(int(nbox), dtype=self.dtype); bu = np.empty(int(nbox), dtype=self.dtype)
+        self._chk(self.lib.cosmo_hip_batch_get_scaled_problem(self._b, int(k), _dp(Pv), _dp(Av), _dp(q), _dp(b), _dp(bl) if nbox else None, _dp(bu) if nbox else None))
+        return Pv, Av, q, b, bl, bu
+
+    def ruiz_info(self):
+        """dict(work_vectors = 'lds' | 'global', lds_bytes, members, rounds) of the device equilibration pass."""
+        out = np.zeros(4, dtype=np.int64)
+        self._chk(self.lib.cosmo_hip_batch_ruiz_info(self._b, out.ctypes.data_as(_PI64)))
+        return dict(work_vectors=("lds", "global")[int(out[0])], lds_bytes=int(out[1]), members=int(out[2]), rounds=int(out[3]))
+
     def stage_qb(self, k, q=None, b=None):
         """Stage the RAW (unscaled) q and / or b of member k for the next apply_updates (host only)."""
         self._chk(self.lib.cosmo_hip_batch_stage_qb(self._b, int(k), _dp(self._f(q, self.n, "q")), _dp(self._f(b, self.m, "b"))))
@@ -876,6 +908,17 @@ class BatchGroup:
     def set_direct(self, on=True):
         """cosmo_hip_batch_group_set_direct: every class's batch takes kkt_kind DIRECT (default ordering); before set_params."""
         self._chk(self.lib.cosmo_hip_batch_group_set_direct(self._g, 1 if on else 0))
+
+    def set_device_scaling(self, iterations, min_scaling=1e-4, max_scaling=1e4):
+        """cosmo_hip_batch_group_set_device_scaling: set_params equilibrates every member without a caller's scaling on the device; before set_params."""
+        self._chk(self.lib.cosmo_hip_batch_group_set_device_scaling(self._g, int(iterations), float(min_scaling), float(max_scaling)))
+
+    def get_scaling(self, k):
+        """(D, E, c) of problem k; after set_params."""
+        n, m = self.dims[int(k)]
+        D = np.empty(n, dtype=self.dtype); E = np.empty(m, dtype=self.dtype); c = C.c_double(1.0)
+        self._chk(self.lib.cosmo_hip_batch_group_get_scaling(self._g, int(k), _dp(D), _dp(E), C.byref(c)))
+        return D, E, float(c.value)
 
     def set_params(self, params):
         self._chk(self.lib.cosmo_hip_batch_group_set_params(self._g, C.byref(params)))

@@ -28,6 +28,7 @@
 #include "psdwg.h"
 #include "cone3.h"
 #include "batch_ldl.h"
+#include "batch_ruiz.h"
 
 struct BCtl {                 // per problem, device resident
   int status; int n_rho_updates;
@@ -2295,6 +2296,10 @@ struct cosmo_hip_batch {
   const real *d_D = nullptr, *d_E = nullptr, *d_c = nullptr; const unsigned char* d_nonneg = nullptr;
   std::vector<int32_t> stg_slot, stg_mem, stg_flag; std::vector<real> stg_val;
   unsigned char* d_stage = nullptr;
+  // device Ruiz equilibration of the staging (cosmo_hip_batch_scale_ruiz, batch_ruiz.hip): issymmetric(P) per member (set_problem), the members that
+  // carry a caller's scaling (set_scaling*), whether the pass ran and what it reports (cosmo_hip_batch_ruiz_info)
+  std::vector<char> p_sym, caller_scaled;
+  bool ruiz_done = false; int64_t ruiz_info[4] = {0, 0, 0, 0};
 };
 
 static int32_t bfail(cosmo_hip_batch* b, int32_t code, const char* fmt, ...) {
@@ -2334,7 +2339,7 @@ extern "C" int32_t cosmo_hip_batch_create(cosmo_hip_batch** out, int32_t device_
   if (hipSetDevice(device_id) != hipSuccess || hipStreamCreate(&b->stream) != hipSuccess) { delete b; return COSMO_HIP_ERR_HIP; }
   b->hA.resize(nprob); b->hAT.resize(nprob); b->hPT.resize(nprob);
   b->hq.assign((size_t)nprob * n, 0.0); b->hb.assign((size_t)nprob * m, 0.0);
-  b->have.assign(nprob, 0);
+  b->have.assign(nprob, 0); b->p_sym.assign(nprob, 0); b->caller_scaled.assign(nprob, 0);
   b->hDinv.assign((size_t)nprob * n, 1.0); b->hEinv.assign((size_t)nprob * m, 1.0); b->hcinv.assign(nprob, 1.0);
   b->hD.assign((size_t)nprob * n, 1.0); b->hE.assign((size_t)nprob * m, 1.0); b->hc.assign(nprob, 1.0);
   cosmo_hip_default_params(&b->prm);
@@ -2383,10 +2388,12 @@ extern "C" int32_t cosmo_hip_batch_set_problem(cosmo_hip_batch* b, int64_t k, co
                                                const real* P_nzval, const int64_t* A_colptr, const int64_t* A_rowval,
                                                const real* A_nzval, const real* q, const real* bvec) {
   if (!b || k < 0 || k >= b->nprob || b->finalized) return bfail(b, COSMO_HIP_ERR_INVALID, "batch_set_problem: bad call");
+  if (b->ruiz_done) return bfail(b, COSMO_HIP_ERR_INVALID, "batch_set_problem: after cosmo_hip_batch_scale_ruiz (the staging holds the scaled problems)");
   const int64_t n = b->n, m = b->m;
   HostCsr Pt, Pm;
   int32_t rc = bcsc(b, n, n, P_colptr, P_rowval, P_nzval, Pt, Pm); if (rc) return rc;
   rc = bcsc(b, m, n, A_colptr, A_rowval, A_nzval, b->hAT[k], b->hA[k]); if (rc) return rc;
+  b->p_sym[k] = (Pt.rowptr == Pm.rowptr && Pt.col == Pm.col && Pt.val == Pm.val) ? 1 : 0;      // issymmetric(P), as cosmo_hip_set_problem
   HostCsr& PT = b->hPT[k];
   PT.nrows = (int)n; PT.ncols = (int)(n + m); PT.rowptr.assign(n + 1, 0); PT.split.assign(n, 0);
   PT.col.clear(); PT.val.clear();
@@ -2414,6 +2421,7 @@ extern "C" int32_t cosmo_hip_batch_set_cones(cosmo_hip_batch* b, int64_t ncones,
 extern "C" int32_t cosmo_hip_batch_set_cones_ex(cosmo_hip_batch* b, int64_t ncones, const int32_t* type, const int64_t* dim,
                                                 const real* box_l, const real* box_u, const real* cone_param) {
   if (!b || b->finalized) return bfail(b, COSMO_HIP_ERR_INVALID, "batch_set_cones: bad call");
+  if (b->ruiz_done) return bfail(b, COSMO_HIP_ERR_INVALID, "batch_set_cones: after cosmo_hip_batch_scale_ruiz (the staging holds the scaled Box bounds)");
   ConeTable& C = b->cones; C = ConeTable();
   int64_t off = 0, nbox = 0;
   for (int64_t k = 0; k < ncones; ++k) {
@@ -2442,6 +2450,7 @@ extern "C" int32_t cosmo_hip_batch_set_cones_ex(cosmo_hip_batch* b, int64_t ncon
 
 extern "C" int32_t cosmo_hip_batch_set_scaling(cosmo_hip_batch* b, int64_t k, const real* Dinv, const real* Einv, double cinv) {
   if (!b || k < 0 || k >= b->nprob || b->finalized) return bfail(b, COSMO_HIP_ERR_INVALID, "batch_set_scaling: bad call");
+  if (b->ruiz_done) return bfail(b, COSMO_HIP_ERR_INVALID, "batch_set_scaling: after cosmo_hip_batch_scale_ruiz (the staging holds its D, E and c)");
   if (Dinv) std::copy(Dinv, Dinv + b->n, b->hDinv.begin() + (size_t)k * b->n);
   if (Einv) std::copy(Einv, Einv + b->m, b->hEinv.begin() + (size_t)k * b->m);
   b->hcinv[k] = cinv;
@@ -2449,6 +2458,7 @@ extern "C" int32_t cosmo_hip_batch_set_scaling(cosmo_hip_batch* b, int64_t k, co
   if (Dinv) for (long long i = 0; i < b->n; ++i) b->hD[(size_t)k * b->n + i] = R(1.0) / Dinv[i];
   if (Einv) for (long long i = 0; i < b->m; ++i) b->hE[(size_t)k * b->m + i] = R(1.0) / Einv[i];
   b->hc[k] = (real)(1.0 / cinv);
+  b->caller_scaled[k] = 1;
   return COSMO_HIP_OK;
 }
 
@@ -3570,5 +3580,77 @@ extern "C" int32_t cosmo_hip_batch_get_qb(cosmo_hip_batch* b, int64_t k, real* q
   if (hipSetDevice(b->device) != hipSuccess) return bfail(b, COSMO_HIP_ERR_HIP, "hipSetDevice failed");
   if (q) BHIP(b, hipMemcpy(q, b->D.q + (size_t)k * b->n, (size_t)b->n * sizeof(real), hipMemcpyDeviceToHost));
   if (bvec) BHIP(b, hipMemcpy(bvec, b->D.b + (size_t)k * b->m, (size_t)b->m * sizeof(real), hipMemcpyDeviceToHost));
+  return COSMO_HIP_OK;
+}
+
+// ---- device Ruiz equilibration of the staged members (batch_ruiz.hip): scale_ruiz! (src/scaling.jl:21-116) of all members in one launch ----------
+// After every set_problem and set_cones, before set_params, instead of set_scaling*: the staging then holds the scaled problems, D, E, c and their
+// inverses exactly as if the caller had scaled on the host and called set_scaling_full, and set_params runs unchanged.  A member that already carries
+// a caller's scaling (set_scaling* was called for it) is left as it is.
+extern "C" int32_t cosmo_hip_batch_scale_ruiz(cosmo_hip_batch* b, int64_t iterations, double min_scaling, double max_scaling) {
+  if (!b) return COSMO_HIP_ERR_INVALID;
+  if (b->finalized) return bfail(b, COSMO_HIP_ERR_INVALID, "batch_scale_ruiz: after set_params");
+  if (b->ruiz_done) return bfail(b, COSMO_HIP_ERR_INVALID, "batch_scale_ruiz: the batch is already scaled");
+  if (!b->have_cones) return bfail(b, COSMO_HIP_ERR_INVALID, "batch_scale_ruiz: batch_set_cones first");
+  for (int k = 0; k < b->nprob; ++k) if (!b->have[k]) return bfail(b, COSMO_HIP_ERR_INVALID, "batch_scale_ruiz: problem %d not set", k);
+  if (iterations < 0 || iterations > 2147483647LL || !(min_scaling > 0.0) || !(max_scaling >= min_scaling)) return bfail(b, COSMO_HIP_ERR_INVALID, "batch_scale_ruiz: bad arguments");
+  for (int k = 0; k < b->nprob; ++k)
+    if (!b->caller_scaled[k] && !b->p_sym[k])
+      return bfail(b, COSMO_HIP_ERR_UNSUPPORTED, "batch_scale_ruiz: P of problem %d must be structurally and numerically symmetric (the reference's symmetrize_full! is a host step)", k);
+  if (hipSetDevice(b->device) != hipSuccess) return bfail(b, COSMO_HIP_ERR_HIP, "hipSetDevice failed");
+  BRuizStage S;
+  S.nprob = b->nprob; S.nbox = b->nbox; S.n = b->n; S.m = b->m;
+  S.A = &b->hA; S.AT = &b->hAT; S.PT = &b->hPT; S.q = &b->hq; S.b = &b->hb; S.box_l = &b->hbox_l; S.box_u = &b->hbox_u;
+  S.D = &b->hD; S.E = &b->hE; S.Dinv = &b->hDinv; S.Einv = &b->hEinv; S.c = &b->hc; S.cinv = &b->hcinv;
+  S.cones = &b->cones; S.skip = &b->caller_scaled;
+  const int32_t rc = bruiz_run(S, b->stream, iterations, (real)min_scaling, (real)max_scaling, b->ruiz_info, b->err);
+  if (rc) return rc;
+  b->ruiz_done = true;
+  return COSMO_HIP_OK;
+}
+
+// D (n), E (m) and c of member k as the batch holds them (the caller's, or those of cosmo_hip_batch_scale_ruiz); any pointer may be NULL
+extern "C" int32_t cosmo_hip_batch_get_scaling(cosmo_hip_batch* b, int64_t k, real* D, real* E, double* c) {
+  if (!b || k < 0 || k >= b->nprob) return bfail(b, COSMO_HIP_ERR_INVALID, "batch_get_scaling: bad call");
+  if (D) std::copy(b->hD.begin() + (size_t)k * b->n, b->hD.begin() + (size_t)(k + 1) * b->n, D);
+  if (E) std::copy(b->hE.begin() + (size_t)k * b->m, b->hE.begin() + (size_t)(k + 1) * b->m, E);
+  if (c) *c = (double)b->hc[(size_t)k];
+  return COSMO_HIP_OK;
+}
+
+// The staged problem of member k (before set_params, which releases the staging): the values of P row by row, of A in the CSC order they were given
+// in, q, b and the member's Box bounds; any pointer may be NULL.  INVALID if the three staged copies of a value -- A, A', [P | A'] -- differ in a bit.
+extern "C" int32_t cosmo_hip_batch_get_scaled_problem(cosmo_hip_batch* b, int64_t k, real* P_csr_val, real* A_csc_val, real* q, real* bvec, real* box_l,
+                                                      real* box_u) {
+  if (!b || k < 0 || k >= b->nprob || b->finalized || !b->have[k]) return bfail(b, COSMO_HIP_ERR_INVALID, "batch_get_scaled_problem: bad call (0 <= k < nprob, set_problem first, before set_params)");
+  const HostCsr &A = b->hA[k], &AT = b->hAT[k], &PT = b->hPT[k];
+  const long long n = b->n, m = b->m;
+  std::vector<int> pos(A.rowptr.begin(), A.rowptr.end() - 1);       // the walk of bcsc: the entry of A' in row j, column i is the next one of row i of A
+  real* Pout = P_csr_val;
+  for (long long j = 0; j < n; ++j) {
+    const int t0 = AT.rowptr[j], t1 = AT.rowptr[j + 1], s0 = PT.split[j];
+    if (PT.rowptr[j + 1] - s0 != t1 - t0) return bfail(b, COSMO_HIP_ERR_INVALID, "batch_get_scaled_problem: the staged copies of problem %d differ in structure", (int)k);
+    for (int t = t0; t < t1; ++t) {
+      const real v = AT.val[t], w = PT.val[s0 + (t - t0)], u = A.val[pos[AT.col[t]]++];
+      if (memcmp(&v, &w, sizeof v) != 0 || memcmp(&v, &u, sizeof v) != 0)
+        return bfail(b, COSMO_HIP_ERR_INVALID, "batch_get_scaled_problem: the staged copies of A(%d, %d) of problem %d differ", AT.col[t], (int)j, (int)k);
+    }
+    if (Pout) Pout = std::copy(PT.val.begin() + PT.rowptr[j], PT.val.begin() + s0, Pout);
+  }
+  if (A_csc_val) std::copy(AT.val.begin(), AT.val.end(), A_csc_val);
+  if (q) std::copy(b->hq.begin() + (size_t)k * n, b->hq.begin() + (size_t)(k + 1) * n, q);
+  if (bvec) std::copy(b->hb.begin() + (size_t)k * m, b->hb.begin() + (size_t)(k + 1) * m, bvec);
+  if ((box_l || box_u) && b->nbox) {
+    if (!b->have_cones) return bfail(b, COSMO_HIP_ERR_INVALID, "batch_get_scaled_problem: batch_set_cones first");
+    if (box_l) std::copy(b->hbox_l.begin() + (size_t)k * b->nbox, b->hbox_l.begin() + (size_t)(k + 1) * b->nbox, box_l);
+    if (box_u) std::copy(b->hbox_u.begin() + (size_t)k * b->nbox, b->hbox_u.begin() + (size_t)(k + 1) * b->nbox, box_u);
+  }
+  return COSMO_HIP_OK;
+}
+
+// out = {work vectors of the pass: 0 LDS, 1 global slab; dynamic LDS bytes of its launch; members it scaled; rounds}
+extern "C" int32_t cosmo_hip_batch_ruiz_info(cosmo_hip_batch* b, int64_t out[4]) {
+  if (!b || !out || !b->ruiz_done) return bfail(b, COSMO_HIP_ERR_INVALID, "batch_ruiz_info: cosmo_hip_batch_scale_ruiz first");
+  for (int i = 0; i < 4; ++i) out[i] = b->ruiz_info[i];
   return COSMO_HIP_OK;
 }

@@ -35,6 +35,7 @@ struct GProblem {
   std::vector<real> uq, ub;       // raw q / b staged for a member on its own handle (cosmo_hip_batch_group_stage_qb)
   bool have_uq = false, have_ub = false;
   bool have = false, have_cones = false, have_scaling = false, have_x0 = false, have_s0 = false, have_mu0 = false;
+  bool dev_scaling = false;       // the scaling is the device pass's (cosmo_hip_batch_group_set_device_scaling), not the caller's
   int cls = -1, pos = -1;         // class and position inside the class
   bool dirty = true;              // set_iterates was called for THIS problem since the class last ran (or it never ran)
 };
@@ -58,6 +59,9 @@ struct cosmo_hip_batch_group {
   std::vector<GClass> cls;
   bool finalized = false, aa_on = false;
   bool direct_on = false;         // cosmo_hip_batch_group_set_direct: every class's batch takes kkt_kind DIRECT (cosmo_hip_batch_set_direct)
+  // cosmo_hip_batch_group_set_device_scaling: set_params equilibrates every member without a caller's scaling on the device (cosmo_hip_batch_scale_ruiz
+  // per class batch, cosmo_hip_scale_ruiz per member on its own handle)
+  bool ruiz_on = false; int64_t ruiz_iterations = 0; double ruiz_min = 0.0, ruiz_max = 0.0;
   int last_workers = 0; long long last_jobs = 0, last_merged = 0;     // of the last optimize: worker threads, jobs (merged sets + batch classes + members on their own handles), classes in merged sets
   cosmo_hip_accel_params aa;
   cosmo_hip_params prm;
@@ -171,6 +175,28 @@ extern "C" int32_t cosmo_hip_batch_group_set_direct(cosmo_hip_batch_group* g, in
   return COSMO_HIP_OK;
 }
 
+// scale_ruiz! on the device for every member that has no caller's scaling (cosmo_hip_batch_group_set_scaling*): set_params then calls
+// cosmo_hip_batch_scale_ruiz on every class batch before cosmo_hip_batch_set_params and, for a member that runs on its own handle, cosmo_hip_scale_ruiz
+// before that handle's set_params.  iterations = 0 switches it off again.  Before set_params.
+extern "C" int32_t cosmo_hip_batch_group_set_device_scaling(cosmo_hip_batch_group* g, int64_t iterations, double min_scaling, double max_scaling) {
+  if (!g) return COSMO_HIP_ERR_INVALID;
+  if (g->finalized) return gfail(g, COSMO_HIP_ERR_INVALID, "batch_group_set_device_scaling: after set_params");
+  if (iterations < 0 || !(min_scaling > 0.0) || !(max_scaling >= min_scaling)) return gfail(g, COSMO_HIP_ERR_INVALID, "batch_group_set_device_scaling: bad arguments");
+  g->ruiz_on = iterations > 0; g->ruiz_iterations = iterations; g->ruiz_min = min_scaling; g->ruiz_max = max_scaling;
+  return COSMO_HIP_OK;
+}
+
+// D (n), E (m) and c of problem k (the caller's, or what the device pass of set_params computed); after set_params; any pointer may be NULL
+extern "C" int32_t cosmo_hip_batch_group_get_scaling(cosmo_hip_batch_group* g, int64_t k, real* D, real* E, double* c) {
+  GCHECK(g, k);
+  if (!g->finalized) return gfail(g, COSMO_HIP_ERR_INVALID, "batch_group_get_scaling: set_params first");
+  const GProblem& p = g->prob[(size_t)k];
+  for (long long i = 0; D && i < p.n; ++i) D[i] = !p.have_scaling ? R(1.0) : (p.Dsc.empty() ? R(1.0) / p.Dinv[(size_t)i] : p.Dsc[(size_t)i]);
+  for (long long i = 0; E && i < p.m; ++i) E[i] = !p.have_scaling ? R(1.0) : (p.Esc.empty() ? R(1.0) / p.Einv[(size_t)i] : p.Esc[(size_t)i]);
+  if (c) *c = !p.have_scaling ? 1.0 : (p.c != 0.0 ? p.c : 1.0 / p.cinv);
+  return COSMO_HIP_OK;
+}
+
 // Partitions the problems into classes of identical structure and finalises one cosmo_hip_batch per class -- or, where the batch kernels refuse the
 // structure (COSMO_HIP_ERR_UNSUPPORTED), one single-problem handle per member.  Any other error of a class's set-up, and a member that no path of the
 // library takes, is the group's error with the offending problem named; the group then holds no classes and set_params may be called again.
@@ -180,6 +206,7 @@ extern "C" int32_t cosmo_hip_batch_group_set_params(cosmo_hip_batch_group* g, co
   g->prm = *prm;
   for (auto& c : g->cls) { if (c.b) (void)cosmo_hip_batch_destroy(c.b); for (auto* h : c.hs) if (h) (void)cosmo_hip_destroy(h); }     // (left over from a failed call)
   g->cls.clear();
+  for (auto& p : g->prob) if (p.dev_scaling) { p.have_scaling = p.dev_scaling = false; p.Dsc.clear(); p.Esc.clear(); p.c = 0.0; p.cinv = 1.0; }     // (of a failed call)
   std::map<std::string, int> index;
   for (size_t k = 0; k < g->prob.size(); ++k) {
     GProblem& p = g->prob[k];
@@ -222,7 +249,30 @@ extern "C" int32_t cosmo_hip_batch_group_set_params(cosmo_hip_batch_group* g, co
     rc = cosmo_hip_batch_set_cones_ex(C.b, (int64_t)p0.ctype.size(), p0.ctype.data(), p0.cdim.data(), bl.data(), bu.data(), p0.cparam.data());
     if (rc == COSMO_HIP_OK && g->aa_on) rc = cosmo_hip_batch_set_accelerator(C.b, &g->aa);
     if (rc == COSMO_HIP_OK && g->direct_on) rc = cosmo_hip_batch_set_direct(C.b, 1, nullptr);
+    // The device pass runs before cosmo_hip_batch_set_params, which is where the batch kernels accept or refuse the structure.  What set_params refuses on
+    // the parameters alone is tested here first, so that such a class is not scaled twice (once in vain as a batch, once per own handle); a refusal that
+    // only the set-up itself finds (the storage budget of the direct batch) still costs the pass.  An UNSUPPORTED of the pass (an asymmetric P) is the
+    // group's error: cosmo_hip_scale_ruiz on an own handle would refuse the same member.
+    const bool direct = g->direct_on && prm->kkt_kind == COSMO_HIP_KKT_DIRECT;
+    const bool batch_takes_params = (prm->kkt_kind == COSMO_HIP_KKT_CG || direct) && !(prm->adaptive_rho && prm->adaptive_rho_interval == 0);
+    bool class_ruiz = false;
+    if (rc == COSMO_HIP_OK && g->ruiz_on && batch_takes_params) {
+      for (int k : C.members) if (!g->prob[(size_t)k].have_scaling) class_ruiz = true;
+      if (class_ruiz) rc = cosmo_hip_batch_scale_ruiz(C.b, g->ruiz_iterations, g->ruiz_min, g->ruiz_max);
+      if (rc) return bad(rc, "batch_scale_ruiz");
+    }
     if (rc == COSMO_HIP_OK) rc = cosmo_hip_batch_set_params(C.b, prm);
+    if (rc == COSMO_HIP_OK && class_ruiz) {                  // the members' D, E, c: the getter, and what a later update of a member scales with
+      for (size_t j = 0; j < C.members.size(); ++j) {
+        GProblem& p = g->prob[(size_t)C.members[j]];
+        if (p.have_scaling) continue;
+        p.Dsc.resize((size_t)p.n); p.Esc.resize((size_t)p.m); p.Dinv.resize((size_t)p.n); p.Einv.resize((size_t)p.m);
+        if ((rc = cosmo_hip_batch_get_scaling(C.b, (int64_t)j, p.Dsc.data(), p.Esc.data(), &p.c))) return bad(rc, "batch_get_scaling");
+        for (long long i = 0; i < p.n; ++i) p.Dinv[(size_t)i] = R(1.0) / p.Dsc[(size_t)i];
+        for (long long i = 0; i < p.m; ++i) p.Einv[(size_t)i] = R(1.0) / p.Esc[(size_t)i];
+        p.cinv = (double)(R(1.0) / (real)p.c); p.have_scaling = p.dev_scaling = true;
+      }
+    }
     if (rc == COSMO_HIP_ERR_UNSUPPORTED) {
       // not a structure of the persistent kernels: one single-problem handle per member instead
       const std::string why = cosmo_hip_batch_last_error(C.b);
@@ -241,6 +291,19 @@ extern "C" int32_t cosmo_hip_batch_group_set_params(cosmo_hip_batch_group* g, co
         if ((hr = cosmo_hip_set_problem(h, p.n, p.m, p.Pp.data(), p.Pi.data(), p.Px.data(), p.Ap.data(), p.Ai.data(), p.Ax.data(), p.q.data(), p.b.data()))) return hbad(hr, h, "set_problem", k);
         if ((hr = cosmo_hip_set_cones_ex(h, (int64_t)p.ctype.size(), p.ctype.data(), p.cdim.data(), p.box_l.empty() ? nullptr : p.box_l.data(),
                                          p.box_u.empty() ? nullptr : p.box_u.data(), p.cparam.data()))) return hbad(hr, h, "set_cones", k);
+        if (g->ruiz_on && !p.have_scaling) {                   // scale_ruiz! on the handle's resident problem, as the single-problem set-up does
+          GProblem& pw = g->prob[(size_t)k];
+          pw.Dsc.resize((size_t)p.n); pw.Esc.resize((size_t)p.m);
+          if ((hr = cosmo_hip_scale_ruiz(h, g->ruiz_iterations, g->ruiz_min, g->ruiz_max, pw.Dsc.data(), pw.Esc.data(), &pw.c))) return hbad(hr, h, "scale_ruiz", k);
+          pw.Dinv.resize((size_t)p.n); pw.Einv.resize((size_t)p.m);
+          for (long long i = 0; i < p.n; ++i) pw.Dinv[(size_t)i] = R(1.0) / pw.Dsc[(size_t)i];
+          for (long long i = 0; i < p.m; ++i) pw.Einv[(size_t)i] = R(1.0) / pw.Esc[(size_t)i];
+          pw.cinv = (double)(R(1.0) / (real)pw.c);
+          if ((hr = cosmo_hip_set_params(h, prm, nullptr))) return hbad(hr, h, "set_params", k);
+          pw.have_scaling = pw.dev_scaling = true;
+          if (g->aa_on && (hr = cosmo_hip_set_accelerator(h, &g->aa))) return hbad(hr, h, "set_accelerator", k);
+          continue;
+        }
         if ((hr = cosmo_hip_set_params(h, prm, nullptr))) return hbad(hr, h, "set_params", k);
         if (p.have_scaling) {
           if (!p.Dsc.empty() && !p.Esc.empty()) hr = cosmo_hip_set_scaling_full(h, p.Dsc.data(), p.Dinv.data(), p.Esc.data(), p.Einv.data(), 1.0 / p.cinv, p.cinv);

@@ -470,6 +470,34 @@ function batch_get_qb(::Type{T}, b::Ptr{Cvoid}, k::Integer, n::Integer, m::Integ
     _rcheck(ccall((:cosmo_hip_batch_get_qb, libpath(T)), Int32, (Ptr{Cvoid}, Int64, Ptr{T}, Ptr{T}), b, Int64(k), q, bv), "cosmo_hip_batch_get_qb")
     return q, bv
 end
+# device Ruiz equilibration of a staged batch (csrc/batch_ruiz.hip): after set_problem / set_cones, before set_params, instead of set_scaling*
+batch_scale_ruiz!(::Type{T}, b::Ptr{Cvoid}, iterations::Integer, min_scaling::Real, max_scaling::Real) where {T <: HipFloat} =
+    _rcheck(ccall((:cosmo_hip_batch_scale_ruiz, libpath(T)), Int32, (Ptr{Cvoid}, Int64, Cdouble, Cdouble), b, Int64(iterations), Float64(min_scaling), Float64(max_scaling)),
+            "cosmo_hip_batch_scale_ruiz")
+function batch_get_scaling(::Type{T}, b::Ptr{Cvoid}, k::Integer, n::Integer, m::Integer) where {T <: HipFloat}
+    D = zeros(T, n); E = zeros(T, m); c = Ref{Cdouble}(1.0)
+    _rcheck(ccall((:cosmo_hip_batch_get_scaling, libpath(T)), Int32, (Ptr{Cvoid}, Int64, Ptr{T}, Ptr{T}, Ref{Cdouble}), b, Int64(k), D, E, c), "cosmo_hip_batch_get_scaling")
+    return D, E, c[]
+end
+function batch_get_scaled_problem(::Type{T}, b::Ptr{Cvoid}, k::Integer, nnzP::Integer, nnzA::Integer, n::Integer, m::Integer, nbox::Integer) where {T <: HipFloat}
+    Pv = zeros(T, nnzP); Av = zeros(T, nnzA); q = zeros(T, n); bv = zeros(T, m); bl = zeros(T, nbox); bu = zeros(T, nbox)
+    _rcheck(ccall((:cosmo_hip_batch_get_scaled_problem, libpath(T)), Int32, (Ptr{Cvoid}, Int64, Ptr{T}, Ptr{T}, Ptr{T}, Ptr{T}, Ptr{T}, Ptr{T}), b, Int64(k), Pv, Av, q, bv, bl, bu),
+            "cosmo_hip_batch_get_scaled_problem")
+    return Pv, Av, q, bv, bl, bu
+end
+function batch_ruiz_info(::Type{T}, b::Ptr{Cvoid}) where {T <: HipFloat}
+    out = zeros(Int64, 4)
+    _rcheck(ccall((:cosmo_hip_batch_ruiz_info, libpath(T)), Int32, (Ptr{Cvoid}, Ptr{Int64}), b, out), "cosmo_hip_batch_ruiz_info")
+    return out
+end
+batch_group_set_device_scaling!(::Type{T}, g::Ptr{Cvoid}, iterations::Integer, min_scaling::Real, max_scaling::Real) where {T <: HipFloat} =
+    _rcheck(ccall((:cosmo_hip_batch_group_set_device_scaling, libpath(T)), Int32, (Ptr{Cvoid}, Int64, Cdouble, Cdouble), g, Int64(iterations), Float64(min_scaling),
+                  Float64(max_scaling)), "cosmo_hip_batch_group_set_device_scaling")
+function batch_group_get_scaling(::Type{T}, g::Ptr{Cvoid}, k::Integer, n::Integer, m::Integer) where {T <: HipFloat}
+    D = zeros(T, n); E = zeros(T, m); c = Ref{Cdouble}(1.0)
+    _rcheck(ccall((:cosmo_hip_batch_group_get_scaling, libpath(T)), Int32, (Ptr{Cvoid}, Int64, Ptr{T}, Ptr{T}, Ref{Cdouble}), g, Int64(k), D, E, c), "cosmo_hip_batch_group_get_scaling")
+    return D, E, c[]
+end
 function batch_group_stage_qb!(::Type{T}, g::Ptr{Cvoid}, k::Integer, q::Union{Vector{T}, Nothing}, bvec::Union{Vector{T}, Nothing}) where {T <: HipFloat}
     GC.@preserve q bvec _rcheck(ccall((:cosmo_hip_batch_group_stage_qb, libpath(T)), Int32, (Ptr{Cvoid}, Int64, Ptr{T}, Ptr{T}), g, Int64(k), _rptr(q), _rptr(bvec)),
                                 "cosmo_hip_batch_group_stage_qb")

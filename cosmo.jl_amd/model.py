@@ -126,6 +126,13 @@ class Settings:
     # one factor per member in its persistent workgroup, refactorised there when its rho changes -- same statuses and solutions to solver accuracy as
     # the single handle, not the same bits.  With persistent_kernel=True it also routes optimize() of one small model to that form.
     direct_batch: bool = False
+    # scale_ruiz! of a whole batch on the device (not a field of COSMO.Settings): optimize_batch, BatchSolver and persistent_kernel otherwise equilibrate
+    # every member on the host, one model at a time.  True: the members are uploaded unscaled and one launch scales them all (csrc/batch_ruiz.hip,
+    # cosmo_hip_batch_scale_ruiz), when scaling != 0 and every member that still needs scaling has a symmetric P -- otherwise the host path, silently,
+    # as device_scaling does for one handle.  The models are left as device_scaling leaves them: sm, the scaled q, b and Box bounds, the UNSCALED P and A.
+    # Where no decision of the scaling depends on the order of a sum the result is the host's to the bit; elsewhere it agrees to a few units in the last
+    # place (two means are summed in another order than NumPy's, and a last-place difference of c or of a cone's E feeds the later rounds).
+    batch_device_scaling: bool = False
     # accepted for drop-in compatibility with COSMO.Settings (src/settings.jl:101-139); they do not touch the hot path:
     nearly_ratio: float = 100.0            # only read by the MOI wrapper (is_primal_nearly_feasible, src/MOI_wrapper.jl:558,587)
     adaptive_rho_fraction: float = 0.4     # only with adaptive_rho_interval = 0 (the automatic interval, solver.jl:244-256)
@@ -440,7 +447,7 @@ def _col_maxabs(M, out, reset):
 def _scale_csc(M, L, R):
     if M.nnz:
         cols = np.repeat(np.arange(M.shape[1]), np.diff(M.indptr))
-        f = np.ones(M.nnz)
+        f = np.ones(M.nnz, dtype=M.dtype)
         if L is not None:
             f = L[M.indices]
             if R is not None:
@@ -450,34 +457,39 @@ def _scale_csc(M, L, R):
         M.data *= f
 
 
-def scale_ruiz(P, q, A, b, sets: Sequence[AbstractConvexSet], st: Settings) -> ScaleMatrices:
-    """`scale_ruiz!` (src/scaling.jl:21-116), in place on P, q, A, b and the Box bounds."""
+def scale_ruiz(P, q, A, b, sets: Sequence[AbstractConvexSet], st: Settings, dtype=np.float64, mean=np.mean) -> ScaleMatrices:
+    """`scale_ruiz!` (src/scaling.jl:21-116), in place on P, q, A, b and the Box bounds.  `dtype`: the element type T of the arithmetic (P, q, A, b are
+    then arrays of T; the default is what every caller of the package uses).  `mean`: how the two order-dependent quantities -- mean(column norms of P)
+    per round, mean(E) per scalar-scaled cone -- are taken (tests restate them in other orders)."""
+    T = np.dtype(dtype).type
+    one, lo, hi = T(1.0), T(st.MIN_SCALING), T(st.MAX_SCALING)
     m, n = A.shape
-    D = np.ones(n); E = np.ones(m); c = 1.0
-    Dw = np.ones(n); Ew = np.ones(m)
+    D = np.ones(n, dtype=T); E = np.ones(m, dtype=T); c = one
+    Dw = np.ones(n, dtype=T); Ew = np.ones(m, dtype=T)
     for _ in range(st.scaling):
         _col_maxabs(P, Dw, True); _col_maxabs(A, Dw, False)
         Ew[:] = 0.0
         if A.nnz:
             np.maximum.at(Ew, A.indices, np.abs(A.data))
-        Dw[:] = 1.0 / np.sqrt(_limit(Dw, st.MIN_SCALING, st.MAX_SCALING))
-        Ew[:] = 1.0 / np.sqrt(_limit(Ew, st.MIN_SCALING, st.MAX_SCALING))
+        Dw[:] = one / np.sqrt(_limit(Dw, lo, hi))
+        Ew[:] = one / np.sqrt(_limit(Ew, lo, hi))
         _scale_csc(P, Dw, Dw); _scale_csc(A, Ew, Dw)
         q *= Dw; b *= Ew; D *= Dw; E *= Ew
         _col_maxabs(P, Dw, True)
-        mean_col = float(np.mean(Dw)) if n else 0.0
-        nq = float(np.max(np.abs(q))) if n else 0.0
+        mean_col = T(mean(Dw)) if n else T(0.0)
+        nq = T(np.max(np.abs(q))) if n else T(0.0)
         if mean_col != 0.0 and nq != 0.0:
-            nq = float(_limit(nq, st.MIN_SCALING, st.MAX_SCALING))
-            sc = float(_limit(max(nq, mean_col), st.MIN_SCALING, st.MAX_SCALING))
-            ct = 1.0 / sc
-            P.data *= ct; q *= ct; c *= ct
+            nq = T(_limit(nq, lo, hi))
+            sc = T(_limit(max(nq, mean_col), lo, hi))
+            ct = one / sc
+            P.data *= ct; q *= ct; c = T(c * ct)
+    c = float(c)
     off = 0
     Ew[:] = 1.0
     changed = False
     for K in sets:                                                # rectify_set_scalings! (:129-142)
         if K.kind in _SCALAR_SCALED and K.dim > 0:
-            Ew[off:off + K.dim] = float(np.mean(E[off:off + K.dim])) / E[off:off + K.dim]
+            Ew[off:off + K.dim] = T(mean(E[off:off + K.dim])) / E[off:off + K.dim]
             changed = True
         off += K.dim
     if changed:
@@ -490,7 +502,7 @@ def scale_ruiz(P, q, A, b, sets: Sequence[AbstractConvexSet], st: Settings) -> S
         if K.kind == _ffi.BOX:
             K.l *= E[off:off + K.dim]; K.u *= E[off:off + K.dim]
         off += K.dim
-    return ScaleMatrices(D, 1.0 / D, E, 1.0 / E, c, 1.0 / c)
+    return ScaleMatrices(D, one / D, E, one / E, c, float(one / T(c)))
 
 
 _SORT = {_ffi.ZERO: 1, _ffi.NONNEG: 2, _ffi.BOX: 3, _ffi.SOC: 4, _ffi.PSD_SQUARE: 5, _ffi.PSD_TRIANGLE: 6,
@@ -723,7 +735,10 @@ def setup(model: Model):
 
     def make_handle():
         h = _ffi.Handle(st.device, dtype=getattr(model, "dtype", np.float64))
-        h.set_problem(model.P, model.q, model.A, model.b)
+        # (a model that a batch scaled on the device holds the UNSCALED P and A next to the scaled q, b and bounds, and has no handle yet: the scaling is
+        #  kept and the handle receives c D P D and E A D, as a batch would)
+        Pu, Au = _upload_matrices(model)
+        h.set_problem(Pu, model.q, Au, model.b)
         bl = np.concatenate([K.l for K in model.sets if K.kind == _ffi.BOX] or [np.zeros(0)])
         bu = np.concatenate([K.u for K in model.sets if K.kind == _ffi.BOX] or [np.zeros(0)])
         h.set_cones([K.kind for K in model.sets], [K.dim for K in model.sets], bl, bu,
@@ -871,9 +886,56 @@ def shard_range(n_items: int, rank: int, world: int):
     return lo, lo + base + (1 if rank < rem else 0)
 
 
-def prepare_batch(models: Sequence[Model], device: int, scaling_full: bool = False):
-    """setup! of every problem of a shard (host Ruiz scaling per problem, as the reference does per optimize! call) and upload
-    into one `_ffi.Batch` (csrc/batch.hip), iterates set.  Returns (batch, settings actually used)."""
+def _is_symmetric(P) -> bool:
+    """P is structurally AND numerically symmetric, the rule of cosmo_hip_batch_scale_ruiz (csrc/batch.hip: the stored entries of P and of its transpose
+    are the same three arrays).  Stricter than issymmetric(P): a stored zero at (i, j) with nothing at (j, i) sends the list to the host path."""
+    Pc = P if P.has_sorted_indices else P.copy()
+    if Pc is not P:
+        Pc.sort_indices()
+    Pt = Pc.T.tocsc()
+    Pt.sort_indices()
+    return bool(np.array_equal(Pt.indptr, Pc.indptr) and np.array_equal(Pt.indices, Pc.indices) and np.array_equal(Pt.data, Pc.data))
+
+
+def _batch_device_scaling_applies(models: Sequence[Model], st: Settings) -> bool:
+    """Settings.batch_device_scaling: the device pass scales the members that still need scaling, provided every one of them has a symmetric P (the
+    reference's symmetrize_full! is a host step; the rule of setup() for one handle).  Otherwise the whole list takes the host path."""
+    if not st.batch_device_scaling or st.scaling == 0:
+        return False
+    need = [md for md in models if not md.is_scaled]
+    return bool(need) and all(_is_symmetric(md.P) for md in need)
+
+
+def _adopt_device_scaling(md: Model, D, E, c) -> None:
+    """The state setup() leaves a model in after cosmo_hip_scale_ruiz: sm, the scaled q, b and Box bounds; P and A stay unscaled."""
+    md.sm = ScaleMatrices(D, 1.0 / D, E, 1.0 / E, c, 1.0 / c)
+    md.q = (D * md.q) * c
+    md.b = E * md.b
+    off = 0
+    for K in md.sets:
+        if K.kind == _ffi.BOX:
+            K.l *= E[off:off + K.dim]; K.u *= E[off:off + K.dim]
+        off += K.dim
+    md.is_scaled = True
+    md.device_scaled = True
+
+
+def _upload_matrices(md: Model):
+    """(P, A) as a batch must receive them.  A model whose scaling ran on the device keeps the UNSCALED P and A on the host (device_scaled): when it
+    enters a batch again its scaling is kept, as in the reference's second optimize!, and the scaled matrices c D P D and E A D are formed here once."""
+    if not (md.is_scaled and getattr(md, "device_scaled", False)):
+        return md.P, md.A
+    sm = md.sm
+    D = np.asarray(sm.D, dtype=np.float64); E = np.asarray(sm.E, dtype=np.float64)
+    P = md.P.copy(); A = md.A.copy()
+    _scale_csc(P, D, D); P.data *= sm.c
+    _scale_csc(A, E, D)
+    return P, A
+
+
+def prepare_batch(models: Sequence[Model], device: int, scaling_full: bool = False, _host_scaling: bool = False):
+    """setup! of every problem of a shard (host Ruiz scaling per problem, as the reference does per optimize! call; on the device for all of them at once
+    with Settings.batch_device_scaling) and upload into one `_ffi.Batch` (csrc/batch.hip), iterates set.  Returns (batch, settings actually used)."""
     if not models:
         raise ValueError("prepare_batch: empty shard")
     n, m = models[0].n, models[0].m
@@ -894,21 +956,40 @@ def prepare_batch(models: Sequence[Model], device: int, scaling_full: bool = Fal
     if direct:
         B.set_direct(True, perm)                          # before set_params: the LDL' form of the batch kernels (csrc/batch_ldl.hip)
     bl, bu = [], []
+    on_device = not _host_scaling and _batch_device_scaling_applies(models, st)
+    pending = []                                         # members the device pass scales (uploaded unscaled, no set_scaling*)
     for k, md in enumerate(models):                      # setup! per problem (scaling on the host, as in the reference)
         if st.scaling != 0 and not md.is_scaled:
-            md.sm = scale_ruiz(md.P, md.q, md.A, md.b, md.sets, md.settings); md.is_scaled = True
+            if on_device:
+                pending.append(k)
+            else:
+                md.sm = scale_ruiz(md.P, md.q, md.A, md.b, md.sets, md.settings); md.is_scaled = True
         elif md.sm is None:
             md.sm = ScaleMatrices(np.ones(n), np.ones(n), np.ones(m), np.ones(m), 1.0, 1.0)
-        md.x = md.sm.Dinv * md.x; md.mu = (md.sm.Einv * md.mu) * md.sm.c; md.s = md.sm.E * md.s
-        B.set_problem(k, md.P, md.q, md.A, md.b)
-        if scaling_full:                                  # D, E, c themselves: BatchSolver's device update pass scales with them
+        Pu, Au = _upload_matrices(md)
+        B.set_problem(k, Pu, md.q, Au, md.b)
+        if pending and pending[-1] == k:
+            pass
+        elif scaling_full or getattr(md, "device_scaled", False):     # D, E, c themselves: BatchSolver's device update pass scales with them
             B.set_scaling_full(k, md.sm.D, md.sm.Dinv, md.sm.E, md.sm.Einv, md.sm.c, md.sm.cinv)
         else:
             B.set_scaling(k, md.sm.Dinv, md.sm.Einv, md.sm.cinv)
         bl += [K.l for K in md.sets if K.kind == _ffi.BOX]; bu += [K.u for K in md.sets if K.kind == _ffi.BOX]
     B.set_cones(kinds, dims, np.concatenate(bl) if bl else None, np.concatenate(bu) if bu else None,
                 cone_param=[getattr(K, "alpha", 0.0) for K in models[0].sets])
+    if pending:                                          # scale_ruiz! of all of them in one launch (csrc/batch_ruiz.hip), then D, E, c back
+        try:
+            B.scale_ruiz(st.scaling, st.MIN_SCALING, st.MAX_SCALING)
+        except _ffi.CosmoHipError as e:
+            if _ffi.ERR_NAMES.get(e.code) != "UNSUPPORTED":
+                raise
+            B.close()                                    # the library's symmetry rule refused a member: the whole list takes the host path, silently
+            return prepare_batch(models, device, scaling_full, _host_scaling=True)      # (no model has been touched yet)
+        for k in pending:
+            _adopt_device_scaling(models[k], *B.get_scaling(k))
     B.set_params(_params_from_settings(None, st))
+    for md in models:                                    # scale_variables! (src/scaling.jl:118-123)
+        md.x = md.sm.Dinv * md.x; md.mu = (md.sm.Einv * md.mu) * md.sm.c; md.s = md.sm.E * md.s
     B.set_iterates(np.concatenate([md.x for md in models]), np.concatenate([md.s for md in models]),
                    np.concatenate([md.mu for md in models]))
     return B, st
@@ -990,15 +1071,23 @@ def prepare_batch_group(models: Sequence[Model], device: int):
     _install_accelerator(G, st)
     if _direct_batch_of(st)[0]:
         G.set_direct(True)                                # every class's batch takes the LDL' form (default ordering: the classes differ in size)
+    on_device = _batch_device_scaling_applies(models, st)
+    pending = []                                          # members the device pass of set_params scales (uploaded unscaled, no set_scaling*)
+    if on_device:
+        G.set_device_scaling(st.scaling, st.MIN_SCALING, st.MAX_SCALING)
     for k, md in enumerate(models):
         n, m = md.n, md.m
         if st.scaling != 0 and not md.is_scaled:
-            md.sm = scale_ruiz(md.P, md.q, md.A, md.b, md.sets, md.settings); md.is_scaled = True
+            if on_device:
+                pending.append(k)
+            else:
+                md.sm = scale_ruiz(md.P, md.q, md.A, md.b, md.sets, md.settings); md.is_scaled = True
         elif md.sm is None:
             md.sm = ScaleMatrices(np.ones(n), np.ones(n), np.ones(m), np.ones(m), 1.0, 1.0)
-        md.x = md.sm.Dinv * md.x; md.mu = (md.sm.Einv * md.mu) * md.sm.c; md.s = md.sm.E * md.s
-        G.set_problem(k, md.P, md.q, md.A, md.b)
-        G.set_scaling_full(k, md.sm.D, md.sm.Dinv, md.sm.E, md.sm.Einv, md.sm.c, md.sm.cinv)      # (D, E themselves: a member on its own handle tests its certificates with them)
+        Pu, Au = _upload_matrices(md)
+        G.set_problem(k, Pu, md.q, Au, md.b)
+        if not (pending and pending[-1] == k):
+            G.set_scaling_full(k, md.sm.D, md.sm.Dinv, md.sm.E, md.sm.Einv, md.sm.c, md.sm.cinv)      # (D, E themselves: a member on its own handle tests its certificates with them)
         bl = [K.l for K in md.sets if K.kind == _ffi.BOX]; bu = [K.u for K in md.sets if K.kind == _ffi.BOX]
         G.set_cones(k, [K.kind for K in md.sets], [K.dim for K in md.sets], np.concatenate(bl) if bl else None, np.concatenate(bu) if bu else None,
                     cone_param=[getattr(K, "alpha", 0.0) for K in md.sets])
@@ -1006,7 +1095,10 @@ def prepare_batch_group(models: Sequence[Model], device: int):
     if st.adaptive_rho and st.adaptive_rho_interval == 0:
         prm.setup_time = time.perf_counter() - t_start        # ws.times.setup_time of the problems that run on their own handle (solver.jl:246)
     G.set_params(prm)
+    for k in pending:                                     # D, E, c of the device pass (cosmo_hip_batch_scale_ruiz per class, cosmo_hip_scale_ruiz per own handle)
+        _adopt_device_scaling(models[k], *G.get_scaling(k))
     for k, md in enumerate(models):
+        md.x = md.sm.Dinv * md.x; md.mu = (md.sm.Einv * md.mu) * md.sm.c; md.s = md.sm.E * md.s      # scale_variables! (src/scaling.jl:118-123)
         G.set_iterates(k, md.x, md.s, md.mu)
     return G, st
 
@@ -1034,7 +1126,9 @@ def _solve_shard_on_device(models: Sequence[Model], device: int) -> List[Result]
     if mixed:
         LAST_BATCH_INFO.update(B.run_info())                       # worker threads / jobs of the group's bounded pool, structure classes
         LAST_BATCH_INFO["own_handle_members"] = int(np.sum(B.class_info(with_modes=True)[2] == 1))     # members the batch kernels refused
-    elif _direct_batch_of(st)[0]:
+    else:
+        LAST_BATCH_INFO["kernel_form"] = B.kernel_info()["form"]      # which form of the batch kernels ran (cosmo_hip_batch_kernel_info)
+    if not mixed and _direct_batch_of(st)[0]:
         LAST_BATCH_INFO["direct_info"] = B.direct_info()               # the LDL' form of the batch kernels ran (csrc/batch_ldl.hip)
         LAST_BATCH_INFO["direct_counts"] = B.direct_counts()
     out = _write_back(models, B, rs, st, mixed, t0, t_setup)

@@ -550,6 +550,24 @@ COSMO_HIP_API int32_t cosmo_hip_batch_apply_updates(cosmo_hip_batch* b);
 COSMO_HIP_API int32_t cosmo_hip_batch_update_qb(cosmo_hip_batch* b, int64_t count, const int64_t* members, const cosmo_hip_real* q, const cosmo_hip_real* bvec);
 COSMO_HIP_API int32_t cosmo_hip_batch_warm_restart(cosmo_hip_batch* b);
 COSMO_HIP_API int32_t cosmo_hip_batch_get_qb(cosmo_hip_batch* b, int64_t k, cosmo_hip_real* q /* n or NULL */, cosmo_hip_real* bvec /* m or NULL */);
+/* Device Ruiz equilibration of a batch (csrc/batch_ruiz.hip): scale_ruiz! (src/scaling.jl:21-116) of every member in ONE launch, one workgroup per
+ * member, no host round trip -- the rounds, rectify_set_scalings!, the Box bounds and the reciprocals.
+ * cosmo_hip_batch_scale_ruiz: after every cosmo_hip_batch_set_problem and cosmo_hip_batch_set_cones, before cosmo_hip_batch_set_params and INSTEAD of
+ *   cosmo_hip_batch_set_scaling*: hand over the UNSCALED problems; cosmo_hip_batch_set_params then finalises the scaled ones as if the caller had scaled
+ *   them.  A member for which cosmo_hip_batch_set_scaling* was called keeps that scaling and its data.  INVALID: bad arguments (iterations < 0, min <= 0,
+ *   max < min), a member or the cones missing, a finalised or already scaled batch; UNSUPPORTED: a member whose P is not structurally and numerically
+ *   symmetric (the rule of cosmo_hip_scale_ruiz).  Once it has run, cosmo_hip_batch_set_problem, cosmo_hip_batch_set_cones* and
+ *   cosmo_hip_batch_set_scaling* return INVALID: the staging holds the scaled problems.
+ * cosmo_hip_batch_get_scaling: D (n), E (m) and c of member k (NULL: skip).
+ * cosmo_hip_batch_get_scaled_problem: before set_params; the staged values of P row by row (P_csr_val), of A in the CSC order they were given in
+ *   (A_csc_val), q (n), b (m) and the member's Box bounds (NULL: skip); INVALID if the member's three staged copies of A do not hold bit-identical values.
+ * cosmo_hip_batch_ruiz_info: out = {work vectors D, E, Dwork, Ework of the pass: 0 = LDS, 1 = a slab of global memory per member (they did not fit the
+ *   launch's dynamic LDS), dynamic LDS bytes of the launch, members scaled, rounds}. */
+COSMO_HIP_API int32_t cosmo_hip_batch_scale_ruiz(cosmo_hip_batch* b, int64_t iterations, double min_scaling, double max_scaling);
+COSMO_HIP_API int32_t cosmo_hip_batch_get_scaling(cosmo_hip_batch* b, int64_t k, cosmo_hip_real* D /* n or NULL */, cosmo_hip_real* E /* m or NULL */, double* c);
+COSMO_HIP_API int32_t cosmo_hip_batch_get_scaled_problem(cosmo_hip_batch* b, int64_t k, cosmo_hip_real* P_csr_val, cosmo_hip_real* A_csc_val, cosmo_hip_real* q,
+                                                         cosmo_hip_real* bvec, cosmo_hip_real* box_l, cosmo_hip_real* box_u);
+COSMO_HIP_API int32_t cosmo_hip_batch_ruiz_info(cosmo_hip_batch* b, int64_t out[4]);
 
 /* ---- batches of problems of DIFFERENT structure (csrc/batch_group.hip) ------------------------------------------------------------------
  * The reference's batch is a loop over arbitrary models (src/solver.jl:78).  A group takes every problem with ITS OWN (n, m, cones), partitions
@@ -578,6 +596,12 @@ COSMO_HIP_API int32_t cosmo_hip_batch_group_set_scaling_full(cosmo_hip_batch_gro
 COSMO_HIP_API int32_t cosmo_hip_batch_group_set_accelerator(cosmo_hip_batch_group* g, const cosmo_hip_accel_params* p);
 /* cosmo_hip_batch_set_direct(on, default ordering) for every class's batch; before set_params.  Classes the batch kernels still refuse keep their own handles */
 COSMO_HIP_API int32_t cosmo_hip_batch_group_set_direct(cosmo_hip_batch_group* g, int32_t on);
+/* Device Ruiz equilibration for the group (before set_params; iterations = 0: off): cosmo_hip_batch_group_set_params then calls
+ * cosmo_hip_batch_scale_ruiz on every class batch before cosmo_hip_batch_set_params and cosmo_hip_scale_ruiz on every member that runs on its own handle
+ * before that handle's set_params.  Members for which cosmo_hip_batch_group_set_scaling* was called keep the caller's scaling.
+ * cosmo_hip_batch_group_get_scaling: after set_params; D (n), E (m), c of problem k (NULL: skip). */
+COSMO_HIP_API int32_t cosmo_hip_batch_group_set_device_scaling(cosmo_hip_batch_group* g, int64_t iterations, double min_scaling, double max_scaling);
+COSMO_HIP_API int32_t cosmo_hip_batch_group_get_scaling(cosmo_hip_batch_group* g, int64_t k, cosmo_hip_real* D /* n or NULL */, cosmo_hip_real* E /* m or NULL */, double* c);
 COSMO_HIP_API int32_t cosmo_hip_batch_group_set_params(cosmo_hip_batch_group* g, const cosmo_hip_params* p);
 /* number of structure classes; class_of[k] and mode_of[k] for every problem (nprob entries each, may be NULL): mode 0 = the class runs on a
  * persistent batch kernel, 1 = its structure is outside the batch kernels (PSD side > 64, a MINRES solver kind, ...) and every member is solved
