@@ -91,6 +91,7 @@ SIGNATURES = {
     "cosmo_hip_project": (C.c_int32, [C.c_void_p, _PR, _PI64, _PI32]),
     "cosmo_hip_spmv": (C.c_int32, [C.c_void_p, C.c_int32, _PR, _PR]),
     "cosmo_hip_set_iterates": (C.c_int32, [C.c_void_p, _PR, _PR, _PR]),
+    "cosmo_hip_check_certificates": (C.c_int32, [C.c_void_p, _PR, _PR, _PI32]),
     "cosmo_hip_admm_init": (C.c_int32, [C.c_void_p]),
     "cosmo_hip_admm_iterate": (C.c_int32, [C.c_void_p, C.c_int64]),
     "cosmo_hip_admm_iterate_checked": (C.c_int32, [C.c_void_p, C.c_int64, _PI32]),
@@ -145,6 +146,7 @@ SIGNATURES = {
     "cosmo_hip_batch_get_accel_stats": (C.c_int32, [C.c_void_p, _PI64]),
     "cosmo_hip_batch_get_rho_classes": (C.c_int32, [C.c_void_p, C.c_int64, _PI32]),
     "cosmo_hip_batch_set_iterates": (C.c_int32, [C.c_void_p, _PR, _PR, _PR]),
+    "cosmo_hip_batch_check_certificates": (C.c_int32, [C.c_void_p, _PR, _PR, _PI32]),
     "cosmo_hip_batch_optimize": (C.c_int32, [C.c_void_p, C.POINTER(ResultStruct)]),
     "cosmo_hip_batch_iterate": (C.c_int32, [C.c_void_p, C.c_int64, C.c_int32]),
     "cosmo_hip_batch_get_iterates": (C.c_int32, [C.c_void_p, C.c_int64, _PR, _PR, _PR, _PR]),
@@ -445,6 +447,15 @@ class Handle:
     # ---- loop -------------------------------------------------------------------------------------------------
     def set_iterates(self, x0=None, s0=None, mu0=None):
         self._chk(self.lib.cosmo_hip_set_iterates(self._h, _dp(self._f(x0, self.n)), _dp(self._f(s0, self.m)), _dp(self._f(mu0, self.m))))
+
+    def check_certificates(self, dx, dy):
+        """The infeasibility certificates on given differences dx (n), dy (m) of the scaled iterates: PRIMAL_INFEASIBLE, DUAL_INFEASIBLE or
+        UNDETERMINED.  Overwrites the iterates (set_iterates again before iterating)."""
+        if dx is None or dy is None:
+            raise ValueError("check_certificates needs dx and dy")
+        st = C.c_int32(0)
+        self._chk(self.lib.cosmo_hip_check_certificates(self._h, _dp(self._f(dx, self.n, "dx")), _dp(self._f(dy, self.m, "dy")), C.byref(st)))
+        return int(st.value)
 
     def admm_init(self):
         self._chk(self.lib.cosmo_hip_admm_init(self._h))
@@ -803,6 +814,15 @@ class Batch:
     def set_iterates(self, x0=None, s0=None, mu0=None):
         self._chk(self.lib.cosmo_hip_batch_set_iterates(self._b, _dp(self._f(x0, self.nprob * self.n)), _dp(self._f(s0, self.nprob * self.m)),
                                                         _dp(self._f(mu0, self.nprob * self.m))))
+
+    def check_certificates(self, dx, dy):
+        """Handle.check_certificates for every problem (dx: nprob * n, dy: nprob * m): list of nprob statuses.  Overwrites the iterates."""
+        if dx is None or dy is None:
+            raise ValueError("check_certificates needs dx and dy")
+        st = np.zeros(self.nprob, dtype=np.int32)
+        self._chk(self.lib.cosmo_hip_batch_check_certificates(self._b, _dp(self._f(dx, self.nprob * self.n, "dx")), _dp(self._f(dy, self.nprob * self.m, "dy")),
+                                                              st.ctypes.data_as(_PI32)))
+        return [int(v) for v in st]
 
     def optimize(self):
         res = (ResultStruct * self.nprob)()

@@ -446,7 +446,7 @@ extern "C" int32_t cosmo_hip_set_cones_ex(cosmo_hip_handle* h, int64_t ncones, c
       case COSMO_HIP_PSD_SQUARE:
       case COSMO_HIP_PSD_TRIANGLE:
       case COSMO_HIP_PSD_TRIANGLE_COMPLEX:
-        if (d == 1) for (int64_t i = 0; i < d; ++i) meta[o + i] = 2u;  // 1x1: max(x,0) (convexset.jl:307-308,404-405)
+        if (d == 1) for (int64_t i = 0; i < d; ++i) meta[o + i] = 2u | COSMO_META_PSD1;  // 1x1: max(x,0) (convexset.jl:307-308,404-405); the certificates keep is_pos_def!
         break;
     }
   }
@@ -753,6 +753,30 @@ static int32_t maybe_infeas_check(cosmo_hip_handle* h, long long it) {
     hipLaunchKernelGGL(k_ctl_set_status, dim3(1), dim3(1), 0, h->stream, h->ctl, st);
     CHK(sync_ctl(h));
   }
+  return COSMO_HIP_OK;
+}
+
+// The certificates on GIVEN differences: with w_prev = 0, s = 0, w = [dx; 0] and inf_dy = dy, k_inf_deltas forms exactly dx and dy - rho .* 0,
+// and infeas_check runs unchanged -- no test is restated here.
+extern "C" int32_t cosmo_hip_check_certificates(cosmo_hip_handle* h, const real* dx, const real* dy, int32_t* status_out) {
+  ENTER(h);
+  if (!h->have_cones || !h->have_params || !status_out || (!dx && h->n > 0) || (!dy && h->m > 0))
+    return cosmo_fail(h, COSMO_HIP_ERR_INVALID, "check_certificates: set_cones and set_params first; dx, dy and status_out are required");
+  if (h->comm || h->row_shard) return cosmo_fail(h, COSMO_HIP_ERR_UNSUPPORTED, "check_certificates: not available with a communicator or on a row-sharded handle");
+  const long long n = h->n, m = h->m;
+  CHK(infeas_alloc(h));
+  h->have_iterates = false;                  // the iterates are overwritten: set_iterates before the next iteration
+  HIPCHK(h, hipMemsetAsync(h->w, 0, sizeof(real) * (size_t)(n + m), h->stream));
+  HIPCHK(h, hipMemsetAsync(h->w_prev, 0, sizeof(real) * (size_t)(n + m), h->stream));
+  HIPCHK(h, hipMemsetAsync(h->s, 0, sizeof(real) * (size_t)m, h->stream));
+  CHK(h2d(h, h->w, dx, (size_t)n));
+  CHK(h2d(h, h->inf_dy, dy, (size_t)m));
+  CHK(d2h(h, h->ctl_host, h->ctl, 1));      // an earlier run may have halted the stream: the kernels of the check return at once then
+  h->ctl_host->halt = 0; h->ctl_host->status = 0; h->ctl_host->stalled = 0; h->ctl_host->error = 0;
+  CHK(h2d(h, h->ctl, h->ctl_host, 1));
+  int32_t st = COSMO_HIP_UNDETERMINED;
+  CHK(infeas_check(h, &st));
+  *status_out = st;
   return COSMO_HIP_OK;
 }
 

@@ -2113,7 +2113,7 @@ __device__ __forceinline__ void batch_inf_check_body(const BatchDev& D, const in
       dtb += y * b[i];
       const uint32_t mt = D.meta[i], kind = mt & 3u;
       if (kind == 3u) { const uint32_t j = mt >> 2; box += (fabs(y) > epi && y > R(0.0)) ? y * bu[j] : y * bl[j]; }   // Box support function (convexset.jl:850-856)
-      else if (kind == 2u) { if (-y < -epi) viol = 1; }                                                                // in_dual(-y) of Nonnegatives (:76-78)
+      else if (kind == 2u) { if ((mt & COSMO_META_PSD1) ? !(-y > -epi) : (-y < -epi)) viol = 1; }                      // in_dual(-y) of Nonnegatives (:76-78); 1 x 1 PSD: is_pos_def!(-y + tol) (:324-328, 415-418)
     }
     __syncthreads();
     for (int cI = wv; cI < D.nsoc; cI += BS / 64) {   // in_dual(-y) of SecondOrderCone: ||y[2:]|| <= tol + (-y[1])   (:116-118)
@@ -2153,7 +2153,7 @@ __device__ __forceinline__ void batch_inf_check_body(const BatchDev& D, const in
       const real x = adx[i];
       const uint32_t mt = D.meta[i], kind = mt & 3u;
       if (kind == 1u) { if (fabs(x) > edi) viol = 1; }
-      else if (kind == 2u) { if (x > edi) viol = 1; }
+      else if (kind == 2u) { if ((mt & COSMO_META_PSD1) ? !(x < edi) : (x > edi)) viol = 1; }        // 1 x 1 PSD: is_neg_def!(x, tol) <=> -x + tol > 0 (:331-335, 421-424)
       else if (kind == 3u) { const uint32_t j = mt >> 2; if ((bu[j] == (real)INFINITY && x > edi) || (bl[j] == -(real)INFINITY && x < -edi)) viol = 1; }
     }
     for (int cI = wv; cI < D.nsoc; cI += BS / 64) {   // in_pol_recc of SecondOrderCone: ||x[2:]|| <= tol - x[1]   (:120-122)
@@ -3076,7 +3076,7 @@ extern "C" int32_t cosmo_hip_batch_set_params(cosmo_hip_batch* b, const cosmo_hi
       case COSMO_HIP_ZERO: for (long long i = 0; i < d; ++i) meta[o + i] = 1u; break;
       case COSMO_HIP_NONNEG: for (long long i = 0; i < d; ++i) meta[o + i] = 2u; break;
       case COSMO_HIP_PSD_SQUARE: case COSMO_HIP_PSD_TRIANGLE:
-        if (d == 1) { meta[o] = 2u; break; }                        // the 1-D case is max(x, 0) (convexset.jl:303-305, 404-405)
+        if (d == 1) { meta[o] = 2u | COSMO_META_PSD1; break; }      // the 1-D case is max(x, 0) (convexset.jl:303-305, 404-405); the certificates keep is_pos_def!
         { long long sd = 0;
           if (C.type[k] == COSMO_HIP_PSD_SQUARE) { while ((sd + 1) * (sd + 1) <= d) ++sd; } else { while ((sd + 1) * (sd + 2) / 2 <= d) ++sd; }
           if (sd <= 16) { psd_off.push_back((int)o); psd_d.push_back((int)sd); psd_kind.push_back((int)C.type[k]); }
@@ -3209,6 +3209,37 @@ static int32_t brestart_state(cosmo_hip_batch* b) {
   }
   b->have_iterates = true; b->iters_done = 0;
   return COSMO_HIP_OK;
+}
+
+// The certificates of every problem on GIVEN differences (dx: nprob*n, dy: nprob*m): w_prev = 0, s = 0, w = [dx; 0], inf_dy = dy make the kernel's
+// first pass form exactly dx and dy - rho .* 0; then k_batch_inf_check as the loop launches it (all problems: also on accelerated batches).
+extern "C" int32_t cosmo_hip_batch_check_certificates(cosmo_hip_batch* b, const real* dx, const real* dy, int32_t* status_out) {
+  if (!b || !b->finalized || !status_out || (!dx && b->n > 0) || (!dy && b->m > 0))
+    return bfail(b, COSMO_HIP_ERR_INVALID, "batch_check_certificates: set_params first; dx, dy and status_out are required");
+  if (hipSetDevice(b->device) != hipSuccess) return bfail(b, COSMO_HIP_ERR_HIP, "hipSetDevice failed");
+  const size_t n = (size_t)b->n, m = (size_t)b->m, np = (size_t)b->nprob;
+  b->have_iterates = false;                  // the iterates are overwritten: set_iterates before the next solve
+  std::vector<BCtl> c(np);
+  auto undecide = [&]() -> int32_t {
+    for (auto& x : c) { x.status = 0; x.cost = INFINITY; }
+    BHIP(b, hipMemcpyAsync(b->D.ctl, c.data(), sizeof(BCtl) * np, hipMemcpyHostToDevice, b->stream));
+    BHIP(b, hipStreamSynchronize(b->stream));
+    return COSMO_HIP_OK;
+  };
+  BHIP(b, hipMemcpyAsync(c.data(), b->D.ctl, sizeof(BCtl) * np, hipMemcpyDeviceToHost, b->stream));
+  BHIP(b, hipStreamSynchronize(b->stream));
+  { const int32_t rc = undecide(); if (rc) return rc; }
+  BHIP(b, hipMemsetAsync(b->D.w, 0, sizeof(real) * np * (n + m), b->stream));
+  BHIP(b, hipMemsetAsync(b->D.w_prev, 0, sizeof(real) * np * (n + m), b->stream));
+  if (m > 0) BHIP(b, hipMemsetAsync(b->D.s, 0, sizeof(real) * np * m, b->stream));
+  if (n > 0) BHIP(b, hipMemcpy2DAsync(b->D.w, sizeof(real) * (n + m), dx, sizeof(real) * n, sizeof(real) * n, np, hipMemcpyHostToDevice, b->stream));
+  if (m > 0) BHIP(b, hipMemcpyAsync(b->D.inf_dy, dy, sizeof(real) * np * m, hipMemcpyHostToDevice, b->stream));
+  hipLaunchKernelGGL(k_batch_inf_check, dim3(b->nprob), dim3(COSMO_BS), 0, b->stream, b->D, (real)b->prm.eps_prim_inf, (real)b->prm.eps_dual_inf, 0);
+  BHIP(b, hipGetLastError());
+  BHIP(b, hipMemcpyAsync(c.data(), b->D.ctl, sizeof(BCtl) * np, hipMemcpyDeviceToHost, b->stream));
+  BHIP(b, hipStreamSynchronize(b->stream));
+  for (size_t k = 0; k < np; ++k) status_out[k] = c[k].status;
+  return undecide();
 }
 
 extern "C" int32_t cosmo_hip_batch_set_accelerator(cosmo_hip_batch* b, const cosmo_hip_accel_params* p) {

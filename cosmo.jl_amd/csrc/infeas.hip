@@ -93,7 +93,7 @@ __global__ __launch_bounds__(COSMO_BS) void k_inf_adx(CsrView A, const real* __r
 }
 
 // primal certificate pieces on the simple rows: dyn = dy * (-1/norm) (in place) ; <dyn, b> ; Box support function ;
-// in_dual(-dyn) violations of Nonnegatives rows.  meta: kind | boxindex << 2 (1x1 PSD rows are marked kind 2 as well).
+// in_dual(-dyn) violations of Nonnegatives rows.  meta: kind | boxindex << 2 (1x1 PSD rows are kind 2 with COSMO_META_PSD1 set).
 __global__ __launch_bounds__(COSMO_BS) void k_inf_primal_rows(long long m, real fneg, real tol, const uint32_t* __restrict__ meta,
                                                               const real* __restrict__ bl, const real* __restrict__ bu,
                                                               const real* __restrict__ b, real* __restrict__ dy,
@@ -110,7 +110,8 @@ __global__ __launch_bounds__(COSMO_BS) void k_inf_primal_rows(long long m, real 
       const uint32_t j = mt >> 2;
       box += (fabs(y) > tol && y > R(0.0)) ? y * bu[j] : y * bl[j];
     } else if (kind == 2u) {                          // Nonnegatives: in_dual(-y): !any(x < -tol) (convexset.jl:76-78)
-      if (-y < -tol) viol = 1;
+      // a 1 x 1 PSD cone keeps its own test, is_pos_def!(-y + tol): the Cholesky factor exists iff -y + tol > 0 (convexset.jl:324-328, 415-418, algebra.jl:226-233)
+      if ((mt & COSMO_META_PSD1) ? !(-y > -tol) : (-y < -tol)) viol = 1;
     }
   }
   dtb = block_sum(dtb, red); box = block_sum(box, red);
@@ -128,7 +129,7 @@ __global__ __launch_bounds__(COSMO_BS) void k_inf_dual_rows(long long m, real to
     const real x = adx[i];
     const uint32_t mt = meta[i], kind = mt & 3u;
     if (kind == 1u) { if (fabs(x) > tol) viol = 1; }
-    else if (kind == 2u) { if (x > tol) viol = 1; }
+    else if (kind == 2u) { if ((mt & COSMO_META_PSD1) ? !(x < tol) : (x > tol)) viol = 1; }     // 1 x 1 PSD: is_neg_def!(x, tol) <=> -x + tol > 0 (convexset.jl:331-335, 421-424)
     else if (kind == 3u) {
       const uint32_t j = mt >> 2;
       if ((bu[j] == INFINITY && x > tol) || (bl[j] == -INFINITY && x < -tol)) viol = 1;

@@ -41,6 +41,9 @@ typedef double2 real2;
 #define COSMO_BS 256            // threads per workgroup for streaming kernels (4 waves of 64)
 #define COSMO_NNZ_PER_BLOCK 2048 // CSR-stream: nonzeros staged in LDS per row block (16 KB of products; measured best of 512..4096)
 #define COSMO_MAX_PARTIALS 2048 // upper bound on workgroups that emit reduction partials
+// row metadata: kind (2 bits: 0 copy, 1 zero, 2 nonneg, 3 box) | box index << 2.  A 1 x 1 PSD cone projects as kind 2 and carries this bit for the
+// infeasibility certificates, whose test for it is strict (x > -tol) where the Nonnegatives' is not (x >= -tol)
+#define COSMO_META_PSD1 4u
 #define COSMO_NSLOTS 8          // partial-reduction slots
 
 // ---- device control block -------------------------------------------------------------------------------------
@@ -445,6 +448,7 @@ int32_t psd_get_ranks(cosmo_hip_handle* h, int64_t* rank_per_cone);
 int32_t psd_extreme_eigs(cosmo_hip_handle* h, const real* vec, real sign, real tol, std::vector<real>& lam_min);
 static inline bool cone_owned(const cosmo_hip_handle* h, long long k) { return h->cone_hi < 0 || (k >= h->cone_lo && k < h->cone_hi); }
 // infeas.hip
+int32_t infeas_alloc(cosmo_hip_handle* h);
 int32_t infeas_enqueue_capture(cosmo_hip_handle* h);
 int32_t infeas_check(cosmo_hip_handle* h, int32_t* status);
 // comm.hip

@@ -201,7 +201,7 @@ COSMO_HIP_API const char* cosmo_hip_last_error(const cosmo_hip_handle* h);
 /* ABI version of the library (major*1000 + minor).  COSMO_HIP_ABI_VERSION is the version THIS header describes; the bindings generated from
  * it (cosmo.jl_amd/_abi_structs.py, julia/abi_structs.jl) carry the same number and refuse a library that reports another one: a stale
  * .so paired with newer struct mirrors would read garbage, a newer .so would write past an older caller's cosmo_hip_result. */
-#define COSMO_HIP_ABI_VERSION 1004
+#define COSMO_HIP_ABI_VERSION 1005
 COSMO_HIP_API int32_t cosmo_hip_version(void);
 COSMO_HIP_API void cosmo_hip_default_params(cosmo_hip_params* p);
 
@@ -305,6 +305,11 @@ COSMO_HIP_API int32_t cosmo_hip_admm_iterate(cosmo_hip_handle* h, int64_t n_iter
  * This is the timed region of the BASELINE metric (iter_time includes the checks, src/solver.jl:134,169).
  * status_out receives COSMO_HIP_UNDETERMINED or the decided status. */
 COSMO_HIP_API int32_t cosmo_hip_admm_iterate_checked(cosmo_hip_handle* h, int64_t n_iters, int32_t* status_out);
+/* Runs is_primal_infeasible! / is_dual_infeasible! (src/infeasibility.jl) exactly as the loop does after an iteration whose differences are
+ * dx (n) and dy (m), both in the scaled space the loop works in.  status_out: COSMO_HIP_PRIMAL_INFEASIBLE, COSMO_HIP_DUAL_INFEASIBLE or
+ * COSMO_HIP_UNDETERMINED.  Overwrites the iterates: call set_iterates again before iterating or optimizing.  After set_cones and set_params;
+ * not with a communicator or a row shard (ABI 1005). */
+COSMO_HIP_API int32_t cosmo_hip_check_certificates(cosmo_hip_handle* h, const cosmo_hip_real* dx, const cosmo_hip_real* dy, int32_t* status_out);
 /* recover_mu! + calculate_result_info! + calculate_cost! (src/solver.jl:307-310, src/residuals.jl:30-96,
  * 143-153) on the current iterates: out = {r_prim, r_dual, max_norm_prim, max_norm_dual, cost}. */
 COSMO_HIP_API int32_t cosmo_hip_residuals(cosmo_hip_handle* h, double out[5]);
@@ -501,6 +506,10 @@ COSMO_HIP_API int32_t cosmo_hip_batch_set_params(cosmo_hip_batch* b, const cosmo
 COSMO_HIP_API int32_t cosmo_hip_batch_get_rho_classes(cosmo_hip_batch* b, int64_t k, int32_t* cls /* m */);
 /* x0: nprob*n, s0 / mu0: nprob*m, problem-major; NULL = zeros (src/solver.jl:128-129 per problem) */
 COSMO_HIP_API int32_t cosmo_hip_batch_set_iterates(cosmo_hip_batch* b, const cosmo_hip_real* x0, const cosmo_hip_real* s0, const cosmo_hip_real* mu0);
+/* cosmo_hip_check_certificates for every problem of the batch: dx is nprob*n, dy nprob*m, status_out nprob.  Every problem is left undecided
+ * and the iterates are overwritten: call batch_set_iterates before the next solve (ABI 1005). */
+COSMO_HIP_API int32_t cosmo_hip_batch_check_certificates(cosmo_hip_batch* b, const cosmo_hip_real* dx /* nprob*n */, const cosmo_hip_real* dy /* nprob*m */,
+                                                         int32_t* status_out /* nprob */);
 /* optimize! for every problem; results has nprob entries */
 COSMO_HIP_API int32_t cosmo_hip_batch_optimize(cosmo_hip_batch* b, cosmo_hip_result* results);
 /* n_iters more loop bodies on every undecided problem, with the residual checks / adaptive-rho checks of the schedule but WITHOUT the

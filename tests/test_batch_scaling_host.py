@@ -58,7 +58,7 @@ def test_settings_field_and_bindings():
     for cls, meths in ((cj._ffi.Batch, ("scale_ruiz", "get_scaling", "get_scaled_problem", "ruiz_info")), (cj._ffi.BatchGroup, ("set_device_scaling", "get_scaling"))):
         for mname in meths:
             assert callable(getattr(cls, mname))
-    assert cj._ffi.ABI_VERSION == 1004
+    assert cj._ffi.ABI_VERSION == 1005
 
 
 def test_the_device_pass_applies_only_where_the_single_handle_rule_allows():
