@@ -85,6 +85,8 @@ SIGNATURES = {
     "cosmo_hip_get_accel_restarts": (C.c_int32, [C.c_void_p, _PI64]),
     "cosmo_hip_scale_ruiz": (C.c_int32, [C.c_void_p, C.c_int64, C.c_double, C.c_double, _PR, _PR, _PD]),
     "cosmo_hip_update_qb": (C.c_int32, [C.c_void_p, _PR, _PR]),
+    "cosmo_hip_update_matrices": (C.c_int32, [C.c_void_p, _PR, _PR, C.c_int32]),
+    "cosmo_hip_update_matrices_info": (C.c_int32, [C.c_void_p, _PI64]),
     "cosmo_hip_get_rho_classes": (C.c_int32, [C.c_void_p, _PI32]),
     "cosmo_hip_get_rho_vec": (C.c_int32, [C.c_void_p, _PR]),
     "cosmo_hip_kkt_solve": (C.c_int32, [C.c_void_p, _PR, _PR, _PI64]),
@@ -294,6 +296,7 @@ class Handle:
         if rc != OK:
             raise CosmoHipError(rc, "cosmo_hip_create failed (no MI355X visible? this library has no CPU path)")
         self.n = self.m = 0
+        self.nnz_P = self.nnz_A = 0
         self.ncones = 0
         self._callbacks = {}
 
@@ -325,6 +328,7 @@ class Handle:
         self._chk(self.lib.cosmo_hip_set_problem(self._h, n, m, pc.ctypes.data_as(_PI64), pr.ctypes.data_as(_PI64), _dp(pv),
                                                  ac.ctypes.data_as(_PI64), ar.ctypes.data_as(_PI64), _dp(av), _dp(q), _dp(b)))
         self.n, self.m = n, m
+        self.nnz_P, self.nnz_A = int(pv.size), int(av.size)
 
     def set_cones(self, types, dims, box_l=None, box_u=None, cone_param=None):
         t = np.ascontiguousarray(types, dtype=np.int32)
@@ -410,6 +414,17 @@ class Handle:
 
     def update_qb(self, q=None, b=None):
         self._chk(self.lib.cosmo_hip_update_qb(self._h, _dp(self._f(q, self.n)), _dp(self._f(b, self.m))))
+
+    def update_matrices(self, P_data=None, A_data=None, apply_scaling=False):
+        """cosmo_hip_update_matrices: new values of the stored entries of P / A in the order of the CSC arrays set_problem passed (csc_julia: sorted
+        row indices); None = unchanged.  apply_scaling: the handle's D, E, c are applied on the device (the values are the unscaled ones)."""
+        self._chk(self.lib.cosmo_hip_update_matrices(self._h, _dp(self._f(P_data, self.nnz_P, "P_data")), _dp(self._f(A_data, self.nnz_A, "A_data")), 1 if apply_scaling else 0))
+
+    def update_matrices_info(self):
+        out = np.zeros(8, dtype=np.int64)
+        self._chk(self.lib.cosmo_hip_update_matrices_info(self._h, out.ctypes.data_as(_PI64)))
+        return dict(updates=int(out[0]), refreshed_arrays=int(out[1]), host_rebuilds=int(out[2]), bytes_uploaded=int(out[3]), map_bytes=int(out[4]),
+                    analyses=int(out[5]))
 
     def get_rho_classes(self):
         out = np.empty(self.m, dtype=np.int32)

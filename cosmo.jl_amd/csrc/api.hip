@@ -8,6 +8,7 @@
 #include <chrono>
 #include "internal.h"
 #include "device_utils.h"
+#include "value_maps.h"
 
 // ---------------------------------------------------------------------------------------------------------------------
 int32_t cosmo_fail(cosmo_hip_handle* h, int32_t code, const char* fmt, ...) {
@@ -237,6 +238,7 @@ extern "C" int32_t cosmo_hip_destroy(cosmo_hip_handle* h) {
   if (h->stream) (void)hipStreamSynchronize(h->stream);
   free_csr(h->A); free_csr(h->AT); free_csr(h->P); free_csr(h->PT);
   kkt_free(h);
+  upd_free(h);
   (void)cosmo_hip_comm_destroy(h);
   rs_free(h);
   aa_free(h);
@@ -291,6 +293,17 @@ extern "C" int32_t cosmo_hip_set_problem(cosmo_hip_handle* h, int64_t n, int64_t
     for (int k = At.rowptr[j]; k < At.rowptr[j + 1]; ++k) { PT.col[p] = At.col[k] + (int)n; PT.val[p] = At.val[k]; ++p; }
   }
   PT.rowptr[n] = (int)p;
+  // the value maps of cosmo_hip_update_matrices (value_maps.h): source index of every stored entry of A, P and [P | A'] (A' and P' share the
+  // caller's arrays: identity).  Host only; the first update uploads them.
+  std::vector<int> vmA, vmP, vmPT;
+  { std::vector<int> rp, mrp, msp;
+    if (value_map_csr(m, n, A_colptr, A_rowval, rp, vmA) != 0 || rp != Am.rowptr || value_map_csr(n, n, P_colptr, P_rowval, rp, vmP) != 0 || rp != Pm.rowptr)
+      return cosmo_fail(h, COSMO_HIP_ERR_INVALID, "set_problem: the value maps disagree with the staged copies");
+    value_map_merged(n, Pm.rowptr, vmP, A_colptr, mrp, msp, vmPT);
+    if (mrp != PT.rowptr || msp != PT.split) return cosmo_fail(h, COSMO_HIP_ERR_INVALID, "set_problem: the value map of [P | A'] disagrees with the staged copy"); }
+  upd_free(h);
+  h->vm_A.swap(vmA); h->vm_P.swap(vmP); h->vm_PT.swap(vmPT);
+  h->P_pattern_symmetric = (Pt.rowptr == Pm.rowptr && Pt.col == Pm.col);
   kkt_free(h);                       // the reduced operator and the factor's analysis belong to the old pattern
   CHK(upload_csr(h, Am, h->A, (int)n));
   CHK(upload_csr(h, At, h->AT, (int)m));
@@ -310,7 +323,7 @@ extern "C" int32_t cosmo_hip_set_problem(cosmo_hip_handle* h, int64_t n, int64_t
   CHK(dalloc(h, &h->tmp_m, (size_t)m)); CHK(dalloc(h, &h->y2, (size_t)m)); CHK(dalloc(h, &h->io, 2 * N));
   CHK(h2d(h, h->q, q, (size_t)n));
   CHK(h2d(h, h->b, b, (size_t)m));
-  h->has_scaling = false; h->cinv = 1.0;
+  h->has_scaling = false; h->cinv = 1.0; h->cscale = 1.0; h->upd_lost_params = false;
   h->have_problem = true; h->have_cones = false; h->have_params = false; h->have_iterates = false;
   HIPCHK(h, hipMemsetAsync(h->ctl, 0, sizeof(Ctl), h->stream));
   h->host_iter = h->host_solves = 0; h->stalls = 0; h->budget = 12;
@@ -476,6 +489,7 @@ extern "C" int32_t cosmo_hip_set_cones_ex(cosmo_hip_handle* h, int64_t ncones, c
 // ---------------------------------------------------------------------------------------------------------------------
 void free_op_split(cosmo_hip_handle* h) {
   free_csr(h->Am); free_csr(h->PTm);
+  upd_free_split(h);
   dfree(&h->op_mrow); dfree(&h->op_sc_ptr); dfree(&h->op_sc_row); dfree(&h->op_sc_a2); dfree(&h->op_diag); dfree(&h->op_rho_m);
   fold_free(h);
   h->op_split = false; h->op_nsingle = 0;
@@ -498,13 +512,14 @@ int32_t build_op_split(cosmo_hip_handle* h, bool any_a, bool fold, int factor_mi
   // Am: rows with >= 2 nonzeros, compact
   HostCsr Am, AmT, PTm;
   std::vector<int> mrow;
+  std::vector<int> am_src, amt_src, ptm_src;     // positions in A.val / P.val (cosmo_hip_update_matrices)
   Am.ncols = (int)n; Am.rowptr.push_back(0);
   std::vector<int> sc_cnt((size_t)n + 1, 0);
   for (long long i = 0; i < m; ++i) {
     const int len = arp[i + 1] - arp[i];
     if (len >= 2) {
       mrow.push_back((int)i);
-      for (int k = arp[i]; k < arp[i + 1]; ++k) { Am.col.push_back(acol[k]); Am.val.push_back(aval[k]); }
+      for (int k = arp[i]; k < arp[i + 1]; ++k) { Am.col.push_back(acol[k]); Am.val.push_back(aval[k]); am_src.push_back(k); }
       Am.rowptr.push_back((int)Am.col.size());
     } else if (len == 1) {
       sc_cnt[(size_t)acol[arp[i]] + 1]++;
@@ -522,17 +537,17 @@ int32_t build_op_split(cosmo_hip_handle* h, bool any_a, bool fold, int factor_mi
   AmT.nrows = (int)n; AmT.ncols = mm; AmT.rowptr.assign((size_t)n + 1, 0);
   for (int c : Am.col) AmT.rowptr[(size_t)c + 1]++;
   for (long long j = 0; j < n; ++j) AmT.rowptr[j + 1] += AmT.rowptr[j];
-  AmT.col.resize(Am.col.size()); AmT.val.resize(Am.col.size());
+  AmT.col.resize(Am.col.size()); AmT.val.resize(Am.col.size()); amt_src.resize(Am.col.size());
   { std::vector<int> pos(AmT.rowptr.begin(), AmT.rowptr.end() - 1);
-    for (int r = 0; r < mm; ++r) for (int k = Am.rowptr[r]; k < Am.rowptr[r + 1]; ++k) { const int p = pos[Am.col[k]]++; AmT.col[p] = r; AmT.val[p] = Am.val[k]; } }
+    for (int r = 0; r < mm; ++r) for (int k = Am.rowptr[r]; k < Am.rowptr[r + 1]; ++k) { const int p = pos[Am.col[k]]++; AmT.col[p] = r; AmT.val[p] = Am.val[k]; amt_src[p] = am_src[k]; } }
   // merged [P | Am']
   PTm.nrows = (int)n; PTm.ncols = (int)(n + mm); PTm.rowptr.assign((size_t)n + 1, 0); PTm.split.assign((size_t)n, 0);
   PTm.col.reserve((size_t)nnzP + AmT.col.size()); PTm.val.reserve((size_t)nnzP + AmT.col.size());
   for (long long j = 0; j < n; ++j) {
     PTm.rowptr[j] = (int)PTm.col.size();
-    for (int k = prp[j]; k < prp[j + 1]; ++k) { PTm.col.push_back(pcol[k]); PTm.val.push_back(pval[k]); }
+    for (int k = prp[j]; k < prp[j + 1]; ++k) { PTm.col.push_back(pcol[k]); PTm.val.push_back(pval[k]); ptm_src.push_back(k); }
     PTm.split[j] = (int)PTm.col.size();
-    for (int k = AmT.rowptr[j]; k < AmT.rowptr[j + 1]; ++k) { PTm.col.push_back(AmT.col[k] + (int)n); PTm.val.push_back(AmT.val[k]); }
+    for (int k = AmT.rowptr[j]; k < AmT.rowptr[j + 1]; ++k) { PTm.col.push_back(AmT.col[k] + (int)n); PTm.val.push_back(AmT.val[k]); ptm_src.push_back(amt_src[k]); }
   }
   PTm.rowptr[n] = (int)PTm.col.size();
   CHK(upload_csr(h, Am, h->Am, (int)n));
@@ -543,6 +558,7 @@ int32_t build_op_split(cosmo_hip_handle* h, bool any_a, bool fold, int factor_mi
   CHK(h2d(h, h->op_sc_ptr, sc_ptr.data(), (size_t)n + 1)); CHK(h2d(h, h->op_sc_row, sc_row.data(), (size_t)nsingle)); CHK(h2d(h, h->op_sc_a2, sc_a2.data(), (size_t)nsingle));
   h->op_nsingle = nsingle;
   h->op_split = true;
+  h->vm_am.swap(am_src); h->vm_ptm.swap(ptm_src);
   prp.resize((size_t)n + 1);
   if (fold) CHK(fold_build(h, Am, prp, pcol, pval, factor_min));      // assembled operator where Am' rho Am is sparse enough (cg_fold.hip)
   return COSMO_HIP_OK;
@@ -580,6 +596,7 @@ extern "C" int32_t cosmo_hip_set_params(cosmo_hip_handle* h, const cosmo_hip_par
   HIPCHK(h, hipMemsetAsync(h->x_tl, 0, sizeof(real) * (size_t)std::max<long long>(h->n, 1), h->stream));
   HIPCHK(h, hipMemsetAsync(h->nu, 0, sizeof(real) * (size_t)std::max<long long>(h->m, 1), h->stream));
   h->have_params = true;
+  h->upd_lost_params = false;
   // needs the (scaled) matrices and rho: both final from here on.  No route (failed analysis or allocation, a zero pivot or the wrong inertia of
   // the direct solver's factor, an operator Jacobi-PCG cannot use): solves, update_rho and optimize refuse until a set_params succeeds
   const int32_t rc = kkt_configure(h, false);
@@ -628,7 +645,7 @@ extern "C" int32_t cosmo_hip_set_scaling_full(cosmo_hip_handle* h, const real* D
   if (!h->have_problem) return cosmo_fail(h, COSMO_HIP_ERR_INVALID, "set_problem first");
   CHK(upload_or_ones(h, h->Dinv, Dinv, (size_t)h->n)); CHK(upload_or_ones(h, h->Einv, Einv, (size_t)h->m));
   CHK(upload_or_ones(h, h->Dscale, D, (size_t)h->n)); CHK(upload_or_ones(h, h->Escale, E, (size_t)h->m));
-  (void)c;
+  h->cscale = c;
   h->cinv = cinv;
   h->has_scaling = true;
   return COSMO_HIP_OK;

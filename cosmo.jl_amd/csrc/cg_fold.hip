@@ -373,6 +373,7 @@ void fold_free(cosmo_hip_handle* h) {
   if (f->dpos) (void)hipFree(f->dpos);
   if (f->dinv) (void)hipFree(f->dinv);
   free_csr(f->Ad);
+  upd_free_fold(f);
   if (f->tt) (void)hipFree(f->tt);
   if (f->tcur) (void)hipFree(f->tcur);
   if (f->tx) (void)hipFree(f->tx);
@@ -426,17 +427,18 @@ int32_t fold_build(cosmo_hip_handle* h, const HostCsr& Am, const std::vector<int
   std::vector<int> tp((size_t)n + 1, 0);
   for (int cidx : Am.col) tp[(size_t)cidx + 1]++;
   for (long long j = 0; j < n; ++j) tp[j + 1] += tp[j];
-  std::vector<int> trw(Am.col.size());
+  std::vector<int> trw(Am.col.size()), tps(Am.col.size());       // tps: position of the list entry in Am.val (value maps of cosmo_hip_update_matrices)
   std::vector<real> tvl(Am.col.size());
   { std::vector<int> pos(tp.begin(), tp.end() - 1);
-    for (int r = 0; r < mm; ++r) for (int k = Am.rowptr[r]; k < Am.rowptr[r + 1]; ++k) { const int p = pos[Am.col[k]]++; trw[p] = r; tvl[p] = Am.val[k]; } }
+    for (int r = 0; r < mm; ++r) for (int k = Am.rowptr[r]; k < Am.rowptr[r + 1]; ++k) { const int p = pos[Am.col[k]]++; trw[p] = r; tvl[p] = Am.val[k]; tps[p] = k; } }
   HostCsr M;
   M.nrows = (int)n; M.ncols = (int)n; M.rowptr.assign((size_t)n + 1, 0);
   std::vector<real> base;
   std::vector<int> drow, tptr, trow;
   std::vector<real> tprod;
   tptr.push_back(0);
-  struct Term { int j, k; real prod; };
+  struct Term { int j, k; real prod; int pa, pb; };
+  std::vector<int> m_ta, m_tb, m_bptr(1, 0), m_bsrc;
   std::vector<Term> terms;
   std::vector<int> fullcols;
   long long nnz_full = 0;
@@ -446,7 +448,7 @@ int32_t fold_build(cosmo_hip_handle* h, const HostCsr& Am, const std::vector<int
       const int k = trw[q];
       const real aki = tvl[q];
       if (did[(size_t)k] >= 0) continue;                          // a dense row: stays factored (its entry of Ad' is appended behind the columns < n below)
-      for (int p = Am.rowptr[k]; p < Am.rowptr[k + 1]; ++p) terms.push_back({Am.col[p], k, aki * Am.val[p]});
+      for (int p = Am.rowptr[k]; p < Am.rowptr[k + 1]; ++p) terms.push_back({Am.col[p], k, aki * Am.val[p], tps[q], p});
     }
     if (nd > 0) {                                                 // nonzeros row i of the FULLY assembled operator would have (the unit of the bench's algorithmic bytes)
       fullcols.clear();
@@ -469,12 +471,12 @@ int32_t fold_build(cosmo_hip_handle* h, const HostCsr& Am, const std::vector<int
       if (!diag_done) j = std::min(j, (int)i);
       if (j == INT32_MAX) break;
       real b = 0.0;
-      while (ip < ipe && pcol[ip] == j) { b += pval[ip]; ++ip; }      // duplicated entries of P (the C ABI passes them through) are summed, as the SpMV kernels do
-      while (it < terms.size() && terms[it].j == j) { trow.push_back(terms[it].k); tprod.push_back(terms[it].prod); ++it; }
+      while (ip < ipe && pcol[ip] == j) { b += pval[ip]; m_bsrc.push_back(ip); ++ip; }      // duplicated entries of P (the C ABI passes them through) are summed, as the SpMV kernels do
+      while (it < terms.size() && terms[it].j == j) { trow.push_back(terms[it].k); tprod.push_back(terms[it].prod); m_ta.push_back(terms[it].pa); m_tb.push_back(terms[it].pb); ++it; }
       if (j == (int)i) diag_done = true;
       M.col.push_back(j); M.val.push_back(0.0);
       base.push_back(b); drow.push_back(j == (int)i ? (int)i : -1);
-      tptr.push_back((int)trow.size());
+      tptr.push_back((int)trow.size()); m_bptr.push_back((int)m_bsrc.size());
     }
     // the factored part of row i: one entry a_ki rho_k per dense row k that holds column i, at column n + did[k] (ascending: the lists are in Am-row order)
     for (int q = tp[i]; q < tp[i + 1]; ++q) {
@@ -482,8 +484,8 @@ int32_t fold_build(cosmo_hip_handle* h, const HostCsr& Am, const std::vector<int
       if (did[(size_t)k] < 0) continue;
       M.col.push_back((int)n + did[(size_t)k]); M.val.push_back(0.0);
       base.push_back(R(0.0)); drow.push_back(-1);
-      trow.push_back(k); tprod.push_back(tvl[q]);
-      tptr.push_back((int)trow.size());
+      trow.push_back(k); tprod.push_back(tvl[q]); m_ta.push_back(tps[q]); m_tb.push_back(-1);
+      tptr.push_back((int)trow.size()); m_bptr.push_back((int)m_bsrc.size());
     }
     M.rowptr[i + 1] = (int)M.col.size();
   }
@@ -494,12 +496,13 @@ int32_t fold_build(cosmo_hip_handle* h, const HostCsr& Am, const std::vector<int
   f->nterms = (long long)trow.size();
   f->nd = nd;
   f->nnz_full = nd > 0 ? nnz_full : (long long)M.col.size();
+  f->m_ta.swap(m_ta); f->m_tb.swap(m_tb); f->m_bptr.swap(m_bptr); f->m_bsrc.swap(m_bsrc);
   if (nd > 0) {                                                   // the dense rows themselves (values without rho) + their records
     HostCsr Adh;
     Adh.nrows = nd; Adh.ncols = (int)n; Adh.rowptr.assign((size_t)nd + 1, 0);
     for (int r = 0; r < mm; ++r) {
       if (did[(size_t)r] < 0) continue;
-      for (int p = Am.rowptr[r]; p < Am.rowptr[r + 1]; ++p) { Adh.col.push_back(Am.col[p]); Adh.val.push_back(Am.val[p]); }
+      for (int p = Am.rowptr[r]; p < Am.rowptr[r + 1]; ++p) { Adh.col.push_back(Am.col[p]); Adh.val.push_back(Am.val[p]); f->m_ad.push_back(p); }
       Adh.rowptr[(size_t)did[(size_t)r] + 1] = (int)Adh.col.size();
     }
     CHK(upload_csr(h, Adh, f->Ad, (int)n, ADSL * COSMO_BS));

@@ -128,6 +128,12 @@ struct FoldPlan {
   void* sr_chain = nullptr;
   void* sr_chain_cf = nullptr;
   int sr_chain_len = 0;
+  // VALUE MAPS (cosmo_hip_update_matrices; update.hip): where fold_build took every value it stored from, so that new values of P and A refill base, tprod
+  // and Ad.val on the device.  Kept on the host, uploaded by the first update (u_*).
+  std::vector<int> m_ta, m_tb;     // term t: tprod[t] = Am.val[m_ta[t]] * Am.val[m_tb[t]] (m_tb[t] < 0, a factored row's entry: tprod[t] = Am.val[m_ta[t]])
+  std::vector<int> m_bptr, m_bsrc; // base[p] = sum of P.val[m_bsrc[k]], k in [m_bptr[p], m_bptr[p+1]), left to right
+  std::vector<int> m_ad;           // Ad.val[p] = Am.val[m_ad[p]]
+  int *u_ta = nullptr, *u_tb = nullptr, *u_bptr = nullptr, *u_bsrc = nullptr, *u_ad = nullptr;
 };
 
 struct HostCsr {  // host staging of a CSR matrix (0-based)
@@ -288,6 +294,17 @@ struct cosmo_hip_handle {
   // direct KKT solver (ldl.hip): the supernodal factor, built by set_params for kkt_kind COSMO_HIP_KKT_DIRECT
   void* ldl = nullptr;            // LdlPlan
   std::vector<int64_t> kkt_perm;  // cosmo_hip_set_kkt_perm (empty: the default ordering)
+  long long ldl_analyses = 0;     // symbolic analyses this handle has run (ldl_build)
+  // matrix value updates (cosmo_hip_update_matrices; update.hip).  Host maps from set_problem (value_maps.h) and build_op_split; their device copies
+  // (u_*) and the staging of the new values are made by the first update, so a handle that never updates holds nothing of this on the device.
+  std::vector<int> vm_A, vm_P, vm_PT;          // CSR entry of A / P / [P | A'] -> index in the caller's A_nzval / P_nzval
+  bool P_pattern_symmetric = true;             // rowptr / col of P equal those of P' (the values decide P_symmetric)
+  std::vector<int> vm_am, vm_ptm;              // Am.val[p] <- A.val[vm_am[p]]; PTm.val[p] <- P.val / A.val[vm_ptm[p]] (op_sc_a2 follows op_sc_row and A.rowptr)
+  int *u_A = nullptr, *u_P = nullptr, *u_PT = nullptr, *u_am = nullptr, *u_ptm = nullptr;
+  real *u_newP = nullptr, *u_newA = nullptr;   // the uploaded value arrays (nnz(P), nnz(A))
+  double cscale = 1.0;                         // the cost scaling c next to cinv
+  bool upd_lost_params = false;                // a failed update cleared have_params: the next successful one sets it again
+  long long upd_count = 0, upd_refreshed = 0, upd_host_rebuilds = 0, upd_last_bytes = 0;
 };
 
 // ---- error handling ------------------------------------------------------------------------------------------------
@@ -336,6 +353,13 @@ int32_t kkt_enqueue_loop_solve(cosmo_hip_handle* h);            // after k_rhs
 int32_t kkt_solve_now(cosmo_hip_handle* h);                     // ls_x / ls_s uploaded; synchronises
 int32_t kkt_resume(cosmo_hip_handle* h, int extra);             // a stalled loop solve
 bool kkt_krylov_model(const cosmo_hip_handle* h, double* bytes, int* launches);   // time_krylov: false if the route is not timed
+int32_t kkt_update_values(cosmo_hip_handle* h);                 // after new values of P / A reached the four copies
+
+// ---- matrix value updates (update.hip) -----------------------------------------------------------------------------
+int32_t upd_refresh_operator(cosmo_hip_handle* h);              // Am / PTm / op_sc_a2 and base / tprod / Ad.val from the refreshed A.val / P.val
+void upd_free_split(cosmo_hip_handle* h);                       // the split maps (free_op_split)
+void upd_free_fold(FoldPlan* f);                                // the assembled operator's maps on the device (fold_free)
+void upd_free(cosmo_hip_handle* h);                             // everything (set_problem, destroy)
 
 // ---- kernels.hip ---------------------------------------------------------------------------------------------------
 int32_t launch_project_simple_inplace(cosmo_hip_handle* h, real* s);

@@ -115,6 +115,24 @@ int32_t kkt_update_rho(cosmo_hip_handle* h) {
   return rc;
 }
 
+// P.val / A.val and the other resident copies hold new values of the same pattern (cosmo_hip_update_matrices): what the route derived from them follows.
+// No route caches values anywhere else (DESIGN.md "Matrix value updates"): the persistent kernel and both MINRES kinds read the copies themselves, the
+// direct solver refills its panels from P.val / A.val, so no route needs kkt_configure again (upd_host_rebuilds stays 0).
+int32_t kkt_update_values(cosmo_hip_handle* h) {
+  switch (h->route) {
+    case KKT_NONE: return cosmo_fail(h, COSMO_HIP_ERR_INVALID, "update_matrices: the handle has no KKT route (set_params failed)");
+    case KKT_MINRES_FULL: case KKT_MINRES_REDUCED: return COSMO_HIP_OK;
+    case KKT_DIRECT: {
+      const int32_t rc = ldl_refactor_now(h, true);      // same analysis, same plan; the inertia check because the new P may not be convex
+      if (rc != COSMO_HIP_OK) { h->have_params = false; h->have_iterates = false; }
+      return rc;
+    }
+    default:
+      CHK(upd_refresh_operator(h));
+      return refresh_op_split(h);      // k_op_refresh, k_fold_refresh, k_fold_dinv and the padded copy: the rho-dependent values
+  }
+}
+
 // rho may have changed on the device: the diagonal part of A' rho A follows (cheap, unconditional); the direct solver refills and
 // refactorises, each launch a no-op unless rho changed
 int32_t kkt_enqueue_refresh(cosmo_hip_handle* h) {

@@ -229,6 +229,7 @@ static int32_t ldl_build(cosmo_hip_handle* h, const std::vector<int64_t>& perm_r
   if (ldl_analyze(n, m, pr, pc, ar, ac, perm_req.empty() ? nullptr : perm_req.data(), L->S, &err) != 0) {
     return cosmo_fail(h, COSMO_HIP_ERR_INVALID, "direct KKT solver: %s", err);
   }
+  h->ldl_analyses += 1;
   const LdlSymbolic& S = L->S;
   if (S.sn_rp[S.ns] >= 2147483647LL) { return cosmo_fail(h, COSMO_HIP_ERR_UNSUPPORTED, "direct KKT solver: supernode row lists out of int32 range"); }
   // refill maps

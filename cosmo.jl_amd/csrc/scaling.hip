@@ -191,6 +191,7 @@ extern "C" int32_t cosmo_hip_scale_ruiz(cosmo_hip_handle* h, int64_t iterations,
   hipLaunchKernelGGL(k_vec_recip, dim3(egrid(m)), dim3(COSMO_BS), 0, st, m, E, h->Einv);
   HIPCHK(h, hipGetLastError());
   h->cinv = R(1.0) / c;
+  h->cscale = (double)c;
   h->has_scaling = true;
   if (D_out) { HIPCHK(h, hipMemcpyAsync(D_out, D, sizeof(real) * (size_t)n, hipMemcpyDeviceToHost, st)); }
   if (E_out) { HIPCHK(h, hipMemcpyAsync(E_out, E, sizeof(real) * (size_t)m, hipMemcpyDeviceToHost, st)); }

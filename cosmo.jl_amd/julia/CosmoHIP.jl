@@ -128,6 +128,16 @@ function set_problem!(h::Handle{T}, P::SparseMatrixCSC{T, Int64}, A::SparseMatri
     end
 end
 
+# New values for the stored entries of P and / or A (the nzval arrays of matrices with the colptr / rowval set_problem! received; `nothing` =
+# unchanged) on a set-up handle: scaling, rho, iterates and the factor's analysis are kept.  apply_scaling: the values are the UNSCALED ones and
+# the handle applies its D, E, c (after scale_ruiz!); otherwise they are taken as they are (scaled by the caller, as for set_problem!).
+function update_matrices!(h::Handle{T}, Pnz::Union{Vector{T}, Nothing}, Anz::Union{Vector{T}, Nothing}; apply_scaling::Bool = false) where {T <: HipFloat}
+    GC.@preserve Pnz Anz begin
+        check(h, ccall((:cosmo_hip_update_matrices, lib(h)), Int32, (Ptr{Cvoid}, Ptr{T}, Ptr{T}, Int32), h.ptr,
+            Pnz === nothing ? C_NULL : pointer(Pnz), Anz === nothing ? C_NULL : pointer(Anz), Int32(apply_scaling ? 1 : 0)))
+    end
+end
+
 function set_cones!(h::Handle{T}, C::COSMO.CompositeConvexSet{T}) where {T <: HipFloat}
     types = Int32[cone_type(s) for s in C.sets]
     dims = Int64[s.dim for s in C.sets]

@@ -650,8 +650,25 @@ def warm_start_dual(model: Model, y0):
     model.mu[:] = -np.array(y0, dtype=np.float64)                 # src/interface.jl:167
 
 
-def update(model: Model, q=None, b=None):
-    """`COSMO.update!` (src/interface.jl:187-211)."""
+def _same_pattern_csc(model: Model, M, name: str):
+    """M (anything Model.set accepts) as CSC with sorted indices; its STORED pattern must be the model's"""
+    old = getattr(model, name)
+    M = M if sp.issparse(M) else np.atleast_2d(np.asarray(M, dtype=np.float64))
+    M = sp.csc_matrix(M, dtype=np.float64, copy=True)
+    M.sort_indices()
+    if M.shape != old.shape or M.nnz != old.nnz or not np.array_equal(M.indptr, old.indptr) or not np.array_equal(M.indices, old.indices):
+        raise ValueError("The sparsity pattern of %s does not agree with the model's %s (update! changes values only; explicit zeros count as "
+                         "stored entries). Assemble a new model for another pattern." % (name, name))
+    return M
+
+
+def update(model: Model, q=None, b=None, P=None, A=None):
+    """`COSMO.update!` (src/interface.jl:187-211) for q and b, and -- beyond the reference -- new VALUES for P and A on the same sparsity
+    pattern: the handle keeps its set-up (scaling, rho, iterates, the factor's analysis) and refreshes every derived operator on the device
+    (cosmo_hip_update_matrices), so the next optimize() is a warm re-solve.  P / A: anything `Model.set` accepts; converted to CSC with sorted
+    indices, and the stored pattern (indptr, indices) must equal the model's, else ValueError.  Explicit zeros count as stored entries: pass a
+    sparse matrix that keeps them (a dense array drops the zeros of its pattern).  The Ruiz scaling is frozen: if the values change by
+    orders of magnitude, assemble a new model instead."""
     if not model.is_assembled:
         raise RuntimeError("Model has to be assembled once before one can start updating q or b.")
     if q is not None:
@@ -666,14 +683,42 @@ def update(model: Model, q=None, b=None):
             raise ValueError("The dimension of b, does not agree with the model dimension, m.")
         if getattr(model, "chordal", None) is not None:
             raise RuntimeError("Problem vector b can not be updated if the model has been chordally decomposed before.")
+    rb = getattr(model, "resident", None)
+    for name, M in (("P", P), ("A", A)):
+        if M is None:
+            continue
+        if getattr(model, "chordal", None) is not None:
+            raise RuntimeError("Problem matrix %s can not be updated if the model has been chordally decomposed before." % name)
+        if rb is not None:
+            raise NotImplementedError("update(P=, A=): a member of a resident batch (BatchSolver) takes new q and b only; close the batch or "
+                                      "solve the model on its own")
+    if P is not None:
+        P = _same_pattern_csc(model, P, "P")
+    if A is not None:
+        A = _same_pattern_csc(model, A, "A")
     if q is not None:
         model.q = (model.sm.D * q) * model.sm.c if model.is_scaled else q.copy()
     if b is not None:
         model.b = model.sm.E * b if model.is_scaled else b.copy()
-    rb = getattr(model, "resident", None)
+    if P is not None or A is not None:
+        # a model scaled on the device keeps the UNSCALED matrices on the host and lets the handle apply its D, E, c; a host-scaled one
+        # scales the new values here with the kept ScaleMatrices, exactly as scale_ruiz's last step would (c D P D, E A D)
+        on_device = model.is_scaled and getattr(model, "device_scaled", False)
+        if model.is_scaled and not on_device:
+            sm = model.sm
+            if P is not None:
+                _scale_csc(P, sm.D, sm.D); P.data *= sm.c
+            if A is not None:
+                _scale_csc(A, sm.E, sm.D)
+        if P is not None:
+            model.P = P
+        if A is not None:
+            model.A = A
+        if model.handle is not None:
+            model.handle.update_matrices(None if P is None else P.data, None if A is None else A.data, apply_scaling=on_device)
     if rb is not None:
         rb[0]._stage(rb[1], q, b)                                 # a member of a BatchSolver: the raw vectors, scaled by the device update pass
-    elif model.handle is not None:
+    elif model.handle is not None and (q is not None or b is not None):
         model.handle.update_qb(model.q if q is not None else None, model.b if b is not None else None)
 
 

@@ -273,6 +273,22 @@ COSMO_HIP_API int32_t cosmo_hip_get_accel_restarts(cosmo_hip_handle* h, int64_t 
 COSMO_HIP_API int32_t cosmo_hip_scale_ruiz(cosmo_hip_handle* h, int64_t iterations, double min_scaling, double max_scaling, cosmo_hip_real* D_out,
                              cosmo_hip_real* E_out, double* c_out);
 COSMO_HIP_API int32_t cosmo_hip_update_qb(cosmo_hip_handle* h, const cosmo_hip_real* q, const cosmo_hip_real* b);
+/* New values for the stored entries of P and/or A, in the order of the P_nzval / A_nzval arrays cosmo_hip_set_problem received
+ * (same colptr / rowval; NULL = unchanged).  apply_scaling = 0: the values are taken as they are (the caller scaled them, as for
+ * set_problem).  apply_scaling = 1: the handle's D, E, c are applied on the device: A_ij <- a * (E_i * D_j),
+ * P_ij <- (p * (D_i * D_j)) * c  -- the expressions and association of a Ruiz step followed by the cost scaling; on a handle without a
+ * scaling it behaves as 0.  Allowed any time after cosmo_hip_set_problem (before or after set_cones / set_params / scale_ruiz, between
+ * solves).  Like cosmo_hip_update_qb it keeps the pattern, the cones, q, b, the row classes, the scaling vectors, the current rho vector, the
+ * iterates (the next solve is warm), the Krylov warm start, the solve counter and the accelerator; no device array is reallocated.  The
+ * scaling is FROZEN: values that change by orders of magnitude want a new set-up.  With kkt_kind DIRECT the factor is recomputed on the
+ * kept analysis and its inertia checked: an indefinite P fails with COSMO_HIP_ERR_INVALID ("Objective function is not convex.") exactly
+ * as a failed cosmo_hip_update_rho does, and a later valid update or set_params restores the handle.  Row-sharded handles:
+ * COSMO_HIP_ERR_UNSUPPORTED.  Batches and groups have no counterpart. */
+COSMO_HIP_API int32_t cosmo_hip_update_matrices(cosmo_hip_handle* h, const cosmo_hip_real* P_nzval, const cosmo_hip_real* A_nzval, int32_t apply_scaling);
+/* out = {updates applied, derived value arrays refreshed on the device (count over all updates), host rebuilds of the KKT route
+ * caused by updates (0: every route is refreshed on the device), bytes uploaded by the last update, device bytes held by the value maps,
+ * LDL' analyses this handle has run, 0, 0} */
+COSMO_HIP_API int32_t cosmo_hip_update_matrices_info(cosmo_hip_handle* h, int64_t out[8]);
 /* Per-row rho class computed by the library: 0 = rho, 1 = rho*RHO_EQ_OVER_RHO_INEQ, 2 = RHO_MIN
  * (apply_constraint_rho_scaling!, src/parameters.jl:17-49) -- integer bookkeeping, compared bit-exactly. */
 COSMO_HIP_API int32_t cosmo_hip_get_rho_classes(cosmo_hip_handle* h, int32_t* cls /* m */);
