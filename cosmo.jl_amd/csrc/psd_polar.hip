@@ -143,6 +143,10 @@ struct PolarPlan {
   unsigned* d_df_sync = nullptr;
   int df_xoff[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
   int df_grid = 0;
+  int df_pair = 3;           // 1: the queue items are RPairs (two tiles of a block row sharing the row's panel; k_polar_dataflow_pair, 512 threads); 3: the tiles
+                             // that leaves over are paired along the last block column as well; 2 (lab): the same kernel with every tile queued as a single
+                             // item; 0: one ragged tile per item, k_polar_dataflow (256 threads).  COSMO_HIP_POLAR_PAIRED
+  int df_ntiles = 0;         // ragged tiles per product (the items of df_xoff hold one or two of them)
   long long df_launches = 0, df_timed = 0;
   int df_nprod = 0;
   double df_seconds = 0.0;   // event-timed launches (df_timed of them)
@@ -862,6 +866,49 @@ __device__ __forceinline__ void symm_mainloop_r(const real* __restrict__ A, cons
 #undef R_COMPUTE
 }
 
+// the epilogue of one wave's blocks (ragged_tile below describes it; also the epilogue of a half of paired_item)
+template <int EPI, bool SC1>
+__device__ __forceinline__ void ragged_store(const v4d (&acc)[4], const int (&oa)[4], const int (&ob)[4], int nsl, int diag, int i0, int j0, int ld,
+                                             const real* __restrict__ Cin, real* __restrict__ C, real alpha, real beta, int lane) {
+  const int lj = lane & 15;
+#pragma unroll
+  for (int sl = 0; sl < 4; ++sl) {
+    if (sl < nsl) {
+      const int j = ob[sl] + lj;
+      const bool dblk = diag && (oa[sl] == ob[sl]);
+      real v[4];
+      if (EPI == 1) {
+        real c[4];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          const int i = oa[sl] + ACC_ROW(lane, q);
+          const bool ok = !(dblk && i > j);
+          // Cin is exactly symmetric (every iterate is written mirrored from one value): read element (i, j) at its MIRRORED address, where the
+          // 16 lanes of a row group are 128 contiguous bytes (the natural address gives 32-byte pieces)
+          const real* cp = Cin + (ok ? (long long)(i0 + i) * ld + j0 + j : 0);
+          c[q] = SC1 ? __hip_atomic_load(cp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : *cp;      // (SC1: see symm_mainloop_r)
+          if (!ok) c[q] = R(0.0);
+        }
+#pragma unroll
+        for (int q = 0; q < 4; ++q) v[q] = alpha * acc[sl][q] + beta * c[q];
+      } else {
+#pragma unroll
+        for (int q = 0; q < 4; ++q) v[q] = acc[sl][q];
+      }
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        const int i = oa[sl] + ACC_ROW(lane, q);
+        if (!(dblk && i > j)) C[(long long)(j0 + j) * ld + i0 + i] = v[q];
+      }
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        const int i = oa[sl] + ACC_ROW(lane, q);
+        if (!(dblk && i >= j)) C[(long long)(i0 + i) * ld + j0 + j] = v[q];
+      }
+    }
+  }
+}
+
 // one ragged tile of one product: C = alpha A B + beta Cin on the tile's blocks (the whole body of k_symm_gemm_batch_r; also called, tile after tile,
 // by the persistent dependency-driven kernel k_polar_dataflow below -- the same instructions in the same order, hence the same bits)
 // (Measured in round 6 and NOT kept: rotating the block lists over the waves per workgroup -- logical wave 0 carries 1.16x the mean matrix work of a BASELINE
@@ -949,45 +996,7 @@ __device__ __forceinline__ void ragged_tile(const RTile& td, real* __restrict__ 
   // Until round 3 this went through LDS (blocks -> Cs[j][i], barrier, 16 row stores, barrier, 16 mirrored stores per thread): two barriers
   // that wait for the wave with the most blocks, and an epilogue of 8.6 k (7.1 k with batched LDS reads) of a tile's 33.7 k cycles.
   (void)xi; (void)xj;
-  {
-    const int lj = lane & 15;
-#pragma unroll
-    for (int sl = 0; sl < 4; ++sl) {
-      if (sl < nsl) {
-        const int j = ob[sl] + lj;
-        const bool dblk = diag && (oa[sl] == ob[sl]);
-        real v[4];
-        if (EPI == 1) {
-          real c[4];
-#pragma unroll
-          for (int q = 0; q < 4; ++q) {
-            const int i = oa[sl] + ACC_ROW(lane, q);
-            const bool ok = !(dblk && i > j);
-            // Cin is exactly symmetric (every iterate is written mirrored from one value): read element (i, j) at its MIRRORED address, where the
-            // 16 lanes of a row group are 128 contiguous bytes (the natural address gives 32-byte pieces)
-            const real* cp = Cin + (ok ? (long long)(i0 + i) * ld + j0 + j : 0);
-            c[q] = SC1 ? __hip_atomic_load(cp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : *cp;      // (SC1: see symm_mainloop_r)
-            if (!ok) c[q] = R(0.0);
-          }
-#pragma unroll
-          for (int q = 0; q < 4; ++q) v[q] = alpha * acc[sl][q] + beta * c[q];
-        } else {
-#pragma unroll
-          for (int q = 0; q < 4; ++q) v[q] = acc[sl][q];
-        }
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          const int i = oa[sl] + ACC_ROW(lane, q);
-          if (!(dblk && i > j)) C[(long long)(j0 + j) * ld + i0 + i] = v[q];
-        }
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          const int i = oa[sl] + ACC_ROW(lane, q);
-          if (!(dblk && i >= j)) C[(long long)(i0 + i) * ld + j0 + j] = v[q];
-        }
-      }
-    }
-  }
+  ragged_store<EPI, SC1>(acc, oa, ob, nsl, diag, i0, j0, ld, Cin, C, alpha, beta, lane);
 #ifdef POLAR_LAB_TIMING
   { const unsigned long long t_end = RT_NOW();
     RT_ADD(0, t_start); RT_ADD(1, t_first); RT_ADD(2, t_main); RT_ADD(3, t_end); RT_ADD(4, nk);
@@ -1032,12 +1041,153 @@ __device__ __forceinline__ unsigned df_xcc_id() { unsigned x; asm volatile("s_ge
 __device__ __forceinline__ unsigned df_ld(const unsigned* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }     // sc1 load: past the L1, served by the XCD's L2
 // counter read-modify-writes (agent scope; workgroup scope -- executed in the XCD's L2, where all users of a counter sit -- measured the same: 3.891 vs 3.898 ms)
 #define DF_RMW(ptr) __hip_atomic_fetch_add((ptr), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
-template <int OCC>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(OCC, OCC))) void k_polar_dataflow(Ctl* __restrict__ ctl, int guard, const RTile* __restrict__ tiles,
-                                                         const int* __restrict__ cone_nt, unsigned* __restrict__ sync, real* __restrict__ W, const DfArgs a) {
-  extern __shared__ real smem[];
-  __shared__ unsigned s_item;
-  __shared__ int s_fail;
+
+// ---- paired product tiles: two tiles of one block row share the row's operand panel in LDS ------------------------------------------------------
+// A 64 x 64 tile requests two 64-wide panels (16 KB) per k-panel for at most 131 kflop: 8 flop per operand byte out of an L2 that holds almost none of a
+// cone's re-reads, and the launch runs at the pace at which operand bytes arrive.  Tiles (I, J) and (I, J + 1) of a cone read the SAME A panel (block row I).
+// An RPair is a queue item of the 512-thread form of the persistent kernel: waves 0-3 compute tile (I, J) and waves 4-7 tile (I, J + 1), each half with
+// ragged_tile's block-to-wave deal, matrix instruction sequence and k order (hence the same bits); per k-panel the item loads the A panel of part I ONCE and the B
+// panels of J and J + 1 once each -- three part-panels instead of four.  If (I, J) is the diagonal tile of a square product the image of panel I is also its
+// B (SAME of symm_mainloop_r): two part-panels instead of three.  ext1 == 0: a single tile (what is left of a block row after pairing); waves 4-7 then
+// only take part in loads and barriers.  Each of the 512 threads stages ONE pair of reals per panel (symm_mainloop_r: two per panel and thread).
+// What pairing along the rows leaves over lies in the LAST block column (row I has P - I tiles): by default (COSMO_HIP_POLAR_PAIRED=3; 1: rows only) those
+// tiles (I, P - 1), (I', P - 1) ride in one item too and share the column's B panel (profiles/polar_paired_tiles.txt: rows -2.2...-4.0 %, both -3.3 % of the launch).  The kernel does not know which kind of item it runs: it stages the DISTINCT panels
+// among {A of tile 0, B of tile 0, A of tile 1, B of tile 1} -- at most three by construction of the list -- and each half reads its fragments from the
+// images of its two.
+struct alignas(16) RPair { int cone; int i0, j0, i1, j1; int ext0, ext1; int ld, d; int pad; long long woff; };
+
+// Main loop of an item: the DEPTH = 1 pipeline of symm_mainloop_r on np <= 3 panels (np, off[]: workgroup-uniform).  aimg / bimg: the LDS images (stage 0)
+// this wave reads its A / B fragments from.
+template <int NSL, class PreLast>
+__device__ __forceinline__ void pair_mainloop(int ld, int nk, real* smem, v4d (&acc)[4], const int (&oa)[4], const int (&ob)[4], const real* aimg, const real* bimg,
+                                              PreLast pre_last, __amdgpu_buffer_rsrc_t rs, int off0, int off1, int off2, bool ld1, bool ld2) {
+  using Cfg = GemmCfg<64>;
+  constexpr int PITCH = Cfg::PITCH, PANEL = Cfg::PANEL;
+  real* P0s = smem;                             // panel s: stages 2 s, 2 s + 1
+  real* P1s = P0s + 2 * PANEL;
+  real* P2s = P0s + 4 * PANEL;
+  int tid = (int)threadIdx.x;
+  asm volatile("" : "+v"(tid));                // (see symm_mainloop_r: keeps the per-thread offsets out of the registers that live across the item loop)
+  const int lane = tid & 63;
+  const int pstep = PK * ld;
+  const int goff = (tid / 32) * ld + 2 * (tid % 32), soff = (tid / 32) * PITCH + 2 * (tid % 32);
+  real2 r[3] = {make_real2(R(0.0), R(0.0)), make_real2(R(0.0), R(0.0)), make_real2(R(0.0), R(0.0))};
+#define P_LOAD(KB)                                                                                        \
+  {                                                                                                       \
+    const int o_ = (KB) * pstep + goff;                                                                   \
+    r[0] = polar_ld_pair_sc1(rs, (off0 + o_) * (int)sizeof(real));                                        \
+    if (ld1) r[1] = polar_ld_pair_sc1(rs, (off1 + o_) * (int)sizeof(real));                              \
+    if (ld2) r[2] = polar_ld_pair_sc1(rs, (off2 + o_) * (int)sizeof(real));                              \
+  }
+#define P_STORE(BUF)                                                                                      \
+  {                                                                                                       \
+    real* pa_ = P0s + (BUF) * PANEL + soff;                                                                \
+    pa_[0] = r[0].x; pa_[1] = r[0].y;                                                                     \
+    if (ld1) { real* pb_ = P1s + (BUF) * PANEL + soff; pb_[0] = r[1].x; pb_[1] = r[1].y; }                \
+    if (ld2) { real* pb_ = P2s + (BUF) * PANEL + soff; pb_[0] = r[2].x; pb_[1] = r[2].y; }                \
+  }
+  const int fl = lane & 15, fk = lane >> 4;
+  const real* apb[4]; const real* bpb[4];
+#pragma unroll
+  for (int sl = 0; sl < 4; ++sl) { apb[sl] = aimg + fk * PITCH + fl + oa[sl]; bpb[sl] = bimg + fk * PITCH + fl + ob[sl]; }
+#define P_COMPUTE(BUF)                                                                                   \
+  {                                                                                                       \
+    _Pragma("unroll") for (int ks = 0; ks < PK / 4; ++ks) {                                               \
+      real av[NSL > 0 ? NSL : 1], bv[NSL > 0 ? NSL : 1];                                                  \
+      _Pragma("unroll") for (int sl = 0; sl < NSL; ++sl) {                                                \
+        av[sl] = FRAG_RD(apb[sl] + (BUF) * PANEL + ks * 4 * PITCH);                                       \
+        bv[sl] = FRAG_RD(bpb[sl] + (BUF) * PANEL + ks * 4 * PITCH);                                       \
+      }                                                                                                   \
+      _Pragma("unroll") for (int sl = 0; sl < NSL; ++sl) acc[sl] = MFMA_REAL(av[sl], bv[sl], acc[sl]);    \
+    }                                                                                                     \
+  }
+  P_LOAD(0)
+  P_STORE(0)
+  __syncthreads();
+  for (int kb = 0; kb + 1 < nk; kb += 2) {
+    P_LOAD(kb + 1)
+    P_COMPUTE(0)
+    P_STORE(1)
+    __syncthreads();
+    if (kb + 2 >= nk) break;
+    P_LOAD(kb + 2)
+    P_COMPUTE(1)
+    P_STORE(0)
+    __syncthreads();
+  }
+  pre_last();
+  if ((nk - 1) & 1) P_COMPUTE(1) else P_COMPUTE(0)     // (no barrier after the last panel: the epilogue does not touch LDS)
+#undef P_LOAD
+#undef P_STORE
+#undef P_COMPUTE
+}
+
+// one item of one product (512 threads): C = alpha A B + beta Cin on the blocks of its one or two tiles
+template <int EPI, class Hook>
+__device__ __forceinline__ void paired_item(const RPair& td, real* __restrict__ W, int ia, int ib, int icin, int ic, real alpha, real beta, real* smem, Hook pre_last) {
+  constexpr int PANEL = GemmCfg<64>::PANEL;
+  const int ld = td.ld;
+  const long long n2 = (long long)ld * ld;
+  real* base = W + td.woff;
+  const real* Cin = base + icin * n2;
+  real* C = base + ic * n2;
+  const int wv8 = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
+  const int half = wv8 >> 2, wv = wv8 & 3;                         // waves 0-3: the first tile, waves 4-7: the second
+  const int ext = half ? td.ext1 : td.ext0, j0 = half ? td.j1 : td.j0, i0 = half ? td.i1 : td.i0;
+  const int ei = ext & 255, ej = (ext >> 8) & 255, diag = (ext >> 16) & 1;
+  const int nblk = diag ? ei * (ei + 1) / 2 : ei * ej;             // (0 in waves 4-7 of a single tile)
+  int oa[4], ob[4];
+  int nsl = 0;
+#pragma unroll
+  for (int sl = 0; sl < 4; ++sl) {                                 // this wave's blocks: the deal of ragged_tile inside the half
+    const int q = wv + 4 * sl;
+    int bi = 0, bj = 0;
+    if (q < nblk) {
+      nsl = sl + 1;
+      if (diag) { bj = (q >= 6) ? 3 : (q >= 3) ? 2 : (q >= 1) ? 1 : 0; bi = q - bj * (bj + 1) / 2; }
+      else { bj = q / ei; bi = q - bj * ei; }
+    }
+    oa[sl] = 16 * bi; ob[sl] = 16 * bj;
+  }
+  v4d acc[4];
+#pragma unroll
+  for (int sl = 0; sl < 4; ++sl) acc[sl] = v4d{0.0, 0.0, 0.0, 0.0};
+  const int nk = ((td.d + 15) / 16);
+  __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void*)base, 0, (int)(4 * n2 * (long long)sizeof(real)), 0x00020000);
+  // the distinct panels of the item (workgroup-uniform): off[0 .. np), and which of them each operand of each tile is.  The diagonal tile of a square
+  // product has offA == offB (SAME of symm_mainloop_r); two tiles of a block row share their A, two of a block column their B.
+  int off[3] = {(int)(ia * n2) + td.i0, 0, 0};
+  int np = 1;
+  auto slot = [&](int o) {
+    if (o == off[0]) return 0;
+    if (np > 1 && o == off[1]) return 1;
+    if (np > 2 && o == off[2]) return 2;
+    if (np < 3) { off[np] = o; return np++; }
+    return 2;                                  // (not reached: the plan builds no item with four distinct panels)
+  };
+  const int sb0 = slot((int)(ib * n2) + td.j0);
+  int sa1 = 0, sb1 = 0;
+  if (td.ext1) { sa1 = slot((int)(ia * n2) + td.i1); sb1 = slot((int)(ib * n2) + td.j1); }
+  const bool ld1 = np > 1, ld2 = np > 2;              // panels 1 and 2 are staged
+  const real* aimg = smem + 2 * PANEL * (half ? sa1 : 0);
+  const real* bimg = smem + 2 * PANEL * (half ? sb1 : sb0);
+#define P_MAINLOOP(NSL_) pair_mainloop<NSL_>(ld, nk, smem, acc, oa, ob, aimg, bimg, pre_last, rs, off[0], off[1], off[2], ld1, ld2)
+  switch (nsl) {                               // wave-uniform; a wave without a block still takes part in the panel loads and barriers
+    case 4: P_MAINLOOP(4); break;
+    case 3: P_MAINLOOP(3); break;
+    case 2: P_MAINLOOP(2); break;
+    case 1: P_MAINLOOP(1); break;
+    default: P_MAINLOOP(0); break;
+  }
+#undef P_MAINLOOP
+  ragged_store<EPI, true>(acc, oa, ob, nsl, diag, i0, j0, ld, Cin, C, alpha, beta, lane);
+}
+
+// The loop of a persistent workgroup.  PAIR = false: 256 threads, items = ragged tiles (k_polar_dataflow); PAIR = true: 512 threads, items = RPairs
+// (k_polar_dataflow_pair); queue, tickets, counters and waits are the same code, the counters count items.
+template <int OCC, bool PAIR, class Item>
+__device__ __forceinline__ void polar_dataflow_loop(Ctl* __restrict__ ctl, int guard, const Item* __restrict__ tiles, const int* __restrict__ cone_nt,
+                                                    unsigned* __restrict__ sync, real* __restrict__ W, const DfArgs& a, real* smem, unsigned& s_item, int& s_fail) {
   if (guard && ctl->halt) return;
   const int x = (int)df_xcc_id();
   const int x0 = a.xoff[x];
@@ -1066,7 +1216,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(OCC, OCC)))
     const unsigned item = __builtin_amdgcn_readfirstlane(s_item);
     if (item >= total) break;
     const unsigned p = item / n_x, t = item - p * n_x;
-    const RTile td = tiles[x0 + t];
+    const Item td = tiles[x0 + t];
     if (p > 0) {
       if (wave0) {
         if (threadIdx.x == 0) {
@@ -1087,12 +1237,35 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(OCC, OCC)))
     // the operands were written by other CUs of this XCD during this launch: they are read with sc1 loads (L1 bypass), never through this CU's L1
     const DfProd pr = a.prod[p];
     auto hook = [&]() { if (wave0) { if (threadIdx.x == 0) nxt = DF_RMW(sync + 16 * x); } };      // the NEXT ticket: its round trip hides behind the last panel and the epilogue
-    if (pr.epi) ragged_tile<1, OCC, true>(td, W, pr.ia, pr.ib, pr.icin, pr.ic, pr.alpha, pr.beta, smem, hook);
-    else ragged_tile<0, OCC, true>(td, W, pr.ia, pr.ib, pr.icin, pr.ic, pr.alpha, pr.beta, smem, hook);
+    if constexpr (PAIR) {
+      if (pr.epi) paired_item<1>(td, W, pr.ia, pr.ib, pr.icin, pr.ic, pr.alpha, pr.beta, smem, hook);
+      else paired_item<0>(td, W, pr.ia, pr.ib, pr.icin, pr.ic, pr.alpha, pr.beta, smem, hook);
+    } else {
+      if (pr.epi) ragged_tile<1, OCC, true>(td, W, pr.ia, pr.ib, pr.icin, pr.ic, pr.alpha, pr.beta, smem, hook);
+      else ragged_tile<0, OCC, true>(td, W, pr.ia, pr.ib, pr.icin, pr.ic, pr.alpha, pr.beta, smem, hook);
+    }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // this thread's stores have reached the L2 (write-through L1); thread 0: the ticket has arrived
     __syncthreads();                                     // ... and so have everybody's; also protects the LDS panels and s_item against the next item
     prev_cone = td.cone;
   }
+}
+template <int OCC>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(OCC, OCC))) void k_polar_dataflow(Ctl* __restrict__ ctl, int guard, const RTile* __restrict__ tiles,
+                                                         const int* __restrict__ cone_nt, unsigned* __restrict__ sync, real* __restrict__ W, const DfArgs a) {
+  extern __shared__ real smem[];
+  __shared__ unsigned s_item;
+  __shared__ int s_fail;
+  polar_dataflow_loop<OCC, false>(ctl, guard, tiles, cone_nt, sync, W, a, smem, s_item, s_fail);
+}
+// the 512-thread form: two workgroups resident per CU (the same 16 waves per CU and 128 registers per wave), 2 stages x 3 panels of LDS each
+#define DF_PAIR_SMEM (6 * GemmCfg<64>::PANEL * (int)sizeof(real))
+template <int OCC>
+__global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(OCC, OCC))) void k_polar_dataflow_pair(Ctl* __restrict__ ctl, int guard, const RPair* __restrict__ tiles,
+                                                         const int* __restrict__ cone_nt, unsigned* __restrict__ sync, real* __restrict__ W, const DfArgs a) {
+  extern __shared__ real smem[];
+  __shared__ unsigned s_item;
+  __shared__ int s_fail;
+  polar_dataflow_loop<OCC, true>(ctl, guard, tiles, cone_nt, sync, W, a, smem, s_item, s_fail);
 }
 #ifdef POLAR_LAB_TIMING
 }  // namespace
@@ -1627,6 +1800,8 @@ int32_t polar_plan_create(cosmo_hip_handle* h) {
     for (const BatchCone& bc : q->bcones) q->batch_flops_useful += (double)bc.d * bc.d * (bc.d + 1.0);
     if (q->batch_ragged) {
       std::vector<std::vector<RTile>> xl(8);
+      std::vector<std::vector<RPair>> xp(8);       // the items of the persistent launch's 512-thread form
+      if (const char* e = getenv("COSMO_HIP_POLAR_PAIRED")) { const int v = atoi(e); if (v >= 0 && v <= 3) q->df_pair = v; }
       long long load[8] = {0, 0, 0, 0, 0, 0, 0, 0};
       for (int ci : order) {
         const BatchCone& bc = q->bcones[ci];
@@ -1646,6 +1821,29 @@ int32_t polar_plan_create(cosmo_hip_handle* h) {
             load[x] += (long long)slots * nb16;
             q->batch_flops_performed += 2.0 * 256.0 * nblk * 16.0 * nb16;
           }
+        // items: along block row ti the tiles (ti, ti), (ti, ti + 1), ... are taken two at a time -- diagonal + right neighbour, then off-diagonal neighbours;
+        // an odd one is left single.  What is left lies in the last block column: df_pair == 3 takes those tiles two at a time as well (they share the
+        // column's B panel).  df_pair == 2 (lab): every tile single, in the order of the tile list above
+        auto item = [&](int ti, int tj, int ti1, int tj1) {      // tile (ti, tj) and, if ti1 >= 0, tile (ti1, tj1)
+          auto ext = [&](int a, int b) { return (start[a + 1] - start[a]) | ((start[b + 1] - start[b]) << 8) | ((a == b ? 1 : 0) << 16); };
+          RPair it; it.cone = ci; it.i0 = 16 * start[ti]; it.j0 = 16 * start[tj]; it.ld = bc.ld; it.d = bc.d; it.woff = bc.woff; it.pad = 0;
+          it.ext0 = ext(ti, tj);
+          it.i1 = ti1 >= 0 ? 16 * start[ti1] : it.i0; it.j1 = ti1 >= 0 ? 16 * start[tj1] : it.j0;
+          it.ext1 = ti1 >= 0 ? ext(ti1, tj1) : 0;
+          xp[x].push_back(it);
+        };
+        if (q->df_pair == 2) { for (int tj = 0; tj < nt; ++tj) for (int ti = 0; ti <= tj; ++ti) item(ti, tj, -1, -1); }
+        else {
+          int left = -1;                                         // a block row whose last tile waits for a partner in the last column
+          for (int ti = 0; ti < nt; ++ti)
+            for (int tj = ti; tj < nt; tj += 2) {
+              if (tj + 1 < nt) item(ti, tj, ti, tj + 1);
+              else if (q->df_pair != 3) item(ti, tj, -1, -1);
+              else if (left < 0) left = ti;
+              else { item(left, tj, ti, tj); left = -1; }
+            }
+          if (left >= 0) item(left, nt - 1, -1, -1);
+        }
       }
       // Launch order inside an XCD's list = decreasing modelled cost of a tile (k-panels x slots of its fullest wave, in units of a tenth
       // of a slot, + a fixed part for prologue and epilogue): the hardware hands the next workgroup to the first free slot, i.e. it runs
@@ -1662,6 +1860,14 @@ int32_t polar_plan_create(cosmo_hip_handle* h) {
           return (long long)((t.d + 15) / 16) * (10 * slots + 2) + 125;
         };
         for (int x = 0; x < 8; ++x) std::stable_sort(xl[x].begin(), xl[x].end(), [&](const RTile& a, const RTile& b) { return cost(a) > cost(b); });
+        auto pcost = [&](const RPair& it) {            // an item costs what its busier half costs
+          RTile t; t.d = it.d; t.ext = it.ext0;
+          const long long c0 = cost(t);
+          if (!it.ext1) return c0;
+          t.ext = it.ext1;
+          return std::max(c0, cost(t));
+        };
+        for (int x = 0; x < 8; ++x) std::stable_sort(xp[x].begin(), xp[x].end(), [&](const RPair& a, const RPair& b) { return pcost(a) > pcost(b); });
       }
       size_t maxlen = 0;
       for (int x = 0; x < 8; ++x) maxlen = std::max(maxlen, xl[x].size());
@@ -1669,26 +1875,42 @@ int32_t polar_plan_create(cosmo_hip_handle* h) {
       for (int x = 0; x < 8; ++x) for (size_t sl = 0; sl < xl[x].size(); ++sl) rl[8 * sl + x] = xl[x][sl];
       q->nrtiles = (int)rl.size();
       { // the same per-XCD lists, contiguous, for the persistent dependency-driven launch of the main schedule
-        std::vector<RTile> dl;
-        std::vector<int> cnt(q->bcones.size(), 0);
-        for (int x = 0; x < 8; ++x) { q->df_xoff[x] = (int)dl.size(); for (const RTile& t : xl[x]) { dl.push_back(t); cnt[(size_t)t.cone] += 1; } }
-        q->df_xoff[8] = (int)dl.size();
-        if (dl.empty()) dl.push_back(RTile{-1, 0, 0, 0, 0, 0, 0});
-        HIPCHK(h, hipMalloc((void**)&q->d_df_tiles, sizeof(RTile) * dl.size()));
-        HIPCHK(h, hipMemcpy(q->d_df_tiles, dl.data(), sizeof(RTile) * dl.size(), hipMemcpyHostToDevice));
+        std::vector<int> cnt(q->bcones.size(), 0);      // items per cone: what a cone's completion counter gains per product
+        q->df_ntiles = 0;
+        for (int x = 0; x < 8; ++x) q->df_ntiles += (int)xl[x].size();
+        if (q->df_pair) {
+          std::vector<RPair> dl;
+          for (int x = 0; x < 8; ++x) { q->df_xoff[x] = (int)dl.size(); for (const RPair& t : xp[x]) { dl.push_back(t); cnt[(size_t)t.cone] += 1; } }
+          q->df_xoff[8] = (int)dl.size();
+          if (dl.empty()) dl.push_back(RPair{-1, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0});
+          HIPCHK(h, hipMalloc((void**)&q->d_df_tiles, sizeof(RPair) * dl.size()));
+          HIPCHK(h, hipMemcpy(q->d_df_tiles, dl.data(), sizeof(RPair) * dl.size(), hipMemcpyHostToDevice));
+        } else {
+          std::vector<RTile> dl;
+          for (int x = 0; x < 8; ++x) { q->df_xoff[x] = (int)dl.size(); for (const RTile& t : xl[x]) { dl.push_back(t); cnt[(size_t)t.cone] += 1; } }
+          q->df_xoff[8] = (int)dl.size();
+          if (dl.empty()) dl.push_back(RTile{-1, 0, 0, 0, 0, 0, 0});
+          HIPCHK(h, hipMalloc((void**)&q->d_df_tiles, sizeof(RTile) * dl.size()));
+          HIPCHK(h, hipMemcpy(q->d_df_tiles, dl.data(), sizeof(RTile) * dl.size(), hipMemcpyHostToDevice));
+        }
         HIPCHK(h, hipMalloc((void**)&q->d_df_cone_nt, sizeof(int) * std::max<size_t>(cnt.size(), 1)));
         HIPCHK(h, hipMemcpy(q->d_df_cone_nt, cnt.data(), sizeof(int) * cnt.size(), hipMemcpyHostToDevice));
         HIPCHK(h, hipMalloc((void**)&q->d_df_sync, sizeof(unsigned) * (DF_SYNC_DONE + cnt.size())));
         hipDeviceProp_t prop;
         HIPCHK(h, hipGetDeviceProperties(&prop, h->device));
+        // The grid is four workgroups per CU in both forms (the launch shape polar_dataflow_stats reports).  The 256-thread form has them all resident; of the
+        // 512-thread form two per CU are (16 waves per CU either way): they drain the queues, and the other half starts when the first leave, draws a ticket
+        // past the end of its queue and returns -- an item waits only for earlier items of its queue, so nothing depends on who is resident.
+        const int slots = std::max(1, prop.multiProcessorCount) * (q->df_pair ? 2 : 4);      // workgroups resident at a time
         q->df_grid = std::max(1, prop.multiProcessorCount) * 4;
         // DEFAULT: on where every XCD's list holds at least as many tiles as the XCD has workgroup slots (BASELINE config 5: 188 tiles, 128 slots:
         // 4.035 -> 3.897 ms per ADMM iteration, same bits).  A small batch (40 cliques: ~17 tiles per XCD) has nothing to overlap -- its products are
         // already shorter than a launch ramp -- and pays a dependency wait per tile: 1.48 -> 1.79 ms, so it keeps the launch-per-product form.
-        { int nmin = INT32_MAX; for (int x = 0; x < 8; ++x) nmin = std::min(nmin, q->df_xoff[x + 1] - q->df_xoff[x]); q->dataflow = (nmin >= q->df_grid / 8) ? 1 : 0; }
+        { int nmin = INT32_MAX; for (int x = 0; x < 8; ++x) nmin = std::min(nmin, q->df_xoff[x + 1] - q->df_xoff[x]); q->dataflow = (nmin >= slots / 8) ? 1 : 0; }
         if (const char* e = getenv("COSMO_HIP_POLAR_DATAFLOW")) q->dataflow = atoi(e) ? 1 : 0;
         if (const char* e = getenv("COSMO_HIP_POLAR_DATAFLOW_GRID")) { const int v = atoi(e); if (v >= 8 && v <= 8192) q->df_grid = v; }
-        (void)hipFuncSetAttribute((const void*)k_polar_dataflow<4>, hipFuncAttributeMaxDynamicSharedMemorySize, GemmCfg<64>::SMEM); }
+        (void)hipFuncSetAttribute((const void*)k_polar_dataflow<4>, hipFuncAttributeMaxDynamicSharedMemorySize, GemmCfg<64>::SMEM);
+        (void)hipFuncSetAttribute((const void*)k_polar_dataflow_pair<4>, hipFuncAttributeMaxDynamicSharedMemorySize, DF_PAIR_SMEM); }
       HIPCHK(h, hipMalloc((void**)&q->d_rtiles, sizeof(RTile) * rl.size()));
       HIPCHK(h, hipMemcpy(q->d_rtiles, rl.data(), sizeof(RTile) * rl.size(), hipMemcpyHostToDevice));
       q->h_rtiles = malloc(sizeof(RTile) * rl.size());
@@ -1837,8 +2059,12 @@ int32_t polar_enqueue_project_batch(cosmo_hip_handle* h, real* s, int guard) {
     (void)hipGetLastError();
     const bool timed = !q->df_ev_pending;
     if (timed) HIPCHK(h, hipEventRecord(q->df_ev[0], st));
-    hipLaunchKernelGGL((k_polar_dataflow<4>), dim3(q->df_grid), dim3(256), GemmCfg<64>::SMEM, st, h->ctl, guard, (const RTile*)q->d_df_tiles, (const int*)q->d_df_cone_nt,
-                       q->d_df_sync, q->BW, dfa);
+    if (q->df_pair)
+      hipLaunchKernelGGL((k_polar_dataflow_pair<4>), dim3(q->df_grid), dim3(512), DF_PAIR_SMEM, st, h->ctl, guard, (const RPair*)q->d_df_tiles, (const int*)q->d_df_cone_nt,
+                         q->d_df_sync, q->BW, dfa);
+    else
+      hipLaunchKernelGGL((k_polar_dataflow<4>), dim3(q->df_grid), dim3(256), GemmCfg<64>::SMEM, st, h->ctl, guard, (const RTile*)q->d_df_tiles, (const int*)q->d_df_cone_nt,
+                         q->d_df_sync, q->BW, dfa);
     if (timed) { HIPCHK(h, hipEventRecord(q->df_ev[1], st)); q->df_ev_pending = 1; }
     q->df_launches += 1; q->df_nprod = dfa.nprod;
     df = false;                                              // everything behind the main schedule is launched product by product
@@ -2046,7 +2272,7 @@ extern "C" int32_t cosmo_hip_polar_dataflow_stats(cosmo_hip_handle* h, double ou
   }
   out[0] = q->dataflow; out[1] = (double)q->df_launches; out[2] = q->df_nprod; out[3] = (double)q->df_timed;
   out[4] = q->df_timed ? q->df_seconds / (double)q->df_timed : 0.0;
-  out[5] = q->batch_flops_performed * q->df_nprod; out[6] = q->df_grid; out[7] = q->df_xoff[8];
+  out[5] = q->batch_flops_performed * q->df_nprod; out[6] = q->df_grid; out[7] = q->df_ntiles;
   return COSMO_HIP_OK;
 }
 // reset of the timing part (bench: time the launches of the timed window only)

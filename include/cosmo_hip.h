@@ -429,7 +429,9 @@ COSMO_HIP_API int32_t cosmo_hip_time_psd_product(cosmo_hip_handle* h, int32_t wh
  * by default every cone runs the plan's k_lift lifting steps (10 in Float64). */
 /* The main schedule of the batched sign iteration as ONE persistent, dependency-driven launch (csrc/psd_polar.hip: k_polar_dataflow; default where every
  * XCD's tile list is at least as long as its workgroup slots, COSMO_HIP_POLAR_DATAFLOW=0|1 forces it): out = {enabled, launches, products per launch,
- * event-timed launches, average seconds per timed launch (HIP events on the handle's stream), matrix flops performed per launch, workgroups, tiles per product}. */
+ * event-timed launches, average seconds per timed launch (HIP events on the handle's stream), matrix flops performed per launch, workgroups, tiles per product}.
+ * A queue item is two tiles of one cone that share an operand panel, run by one workgroup of 512 threads (k_polar_dataflow_pair; COSMO_HIP_POLAR_PAIRED=3,
+ * the default: pairs along block rows and the last block column; 1: rows only; 2: every tile a single item; 0: the 256-thread kernel, one tile per item). */
 COSMO_HIP_API int32_t cosmo_hip_polar_dataflow_stats(cosmo_hip_handle* h, double out[8]);
 COSMO_HIP_API int32_t cosmo_hip_polar_dataflow_reset_timing(cosmo_hip_handle* h);
 COSMO_HIP_API int32_t cosmo_hip_polar_depth_stats(cosmo_hip_handle* h, int64_t out[8]);
