@@ -55,11 +55,21 @@ static __device__ int exp_project(V3& v, int max_iter, real tol) {
 }
 
 // ---- K_pow(alpha) ---------------------------------------------------------------------------------------------------
+// x^a.  The Float32 instantiation widens, as the reference's Float32 `^` does, and rounds once: the result is the correctly rounded power, the same on
+// every math library.  The Newton steps of pow_project do not converge next to the polar cone (r -> 0), and there a last-place difference of powf
+// moved the Float32 result by 1e-3 of the input (tests/test_gpu_cone3_reference.py, branch_edge_polar).  Float64 is pow() as before.
+__device__ __forceinline__ real pow_r(real x, real a) {
+#ifdef COSMO_HIP_REAL_FLOAT
+  return (real)pow((double)x, (double)a);
+#else
+  return pow(x, a);
+#endif
+}
 __device__ __forceinline__ bool pow_in_cone(V3 v, real a, real tol) {   // :707-713
-  return v.x >= R(0.0) && v.y >= R(0.0) && pow(v.x, a) * pow(v.y, R(1.0) - a) >= fabs(v.z) - tol;
+  return v.x >= R(0.0) && v.y >= R(0.0) && pow_r(v.x, a) * pow_r(v.y, R(1.0) - a) >= fabs(v.z) - tol;
 }
 __device__ __forceinline__ bool pow_in_dual(V3 v, real a, real tol) {   // :716-722
-  return v.x >= -tol && v.y >= -tol && pow(v.x, a) * pow(v.y, R(1.0) - a) >= fabs(v.z) * pow(a, a) * pow(R(1.0) - a, R(1.0) - a) - tol;
+  return v.x >= -tol && v.y >= -tol && pow_r(v.x, a) * pow_r(v.y, R(1.0) - a) >= fabs(v.z) * pow_r(a, a) * pow_r(R(1.0) - a, R(1.0) - a) - tol;
 }
 __device__ __forceinline__ real pow_phic(real c0, real az, real r, real a) {   // :686-688
   return fmax(R(0.5) * (c0 + sqrt(c0 * c0 + R(4.0) * a * r * (az - r))), R(1e-10));
@@ -73,7 +83,7 @@ static __device__ int pow_project(V3& v, real a, int max_iter, real tol) {      
   for (int k = 0; k < max_iter; ++k) {
     phix = pow_phic(x0, az, r, a);
     phiy = pow_phic(y0, az, r, R(1.0) - a);
-    const real prod = pow(phix, a) * pow(phiy, R(1.0) - a);
+    const real prod = pow_r(phix, a) * pow_r(phiy, R(1.0) - a);
     const real phi = prod - r;
     if (fabs(phi) < tol) break;
     const real dphix = a / (R(2.0) * phix - x0) * (az - R(2.0) * r);
