@@ -497,7 +497,7 @@ void free_op_split(cosmo_hip_handle* h) {
 
 // any_a: build the split for ANY A (row-sharded runs need a reduced operator that does not depend on h->A, which becomes a row slice).
 // The rho-dependent values are filled by refresh_op_split (kkt_configure, once the route is final).
-int32_t build_op_split(cosmo_hip_handle* h, bool any_a, bool fold, int factor_min) {
+int32_t build_op_split(cosmo_hip_handle* h, bool any_a, bool fold, int factor_min, long long factor_fill_min) {
   free_op_split(h);
   const long long n = h->n, m = h->m, nnzA = h->A.nnz, nnzP = h->P.nnz;
   if (m == 0 || nnzA == 0) return COSMO_HIP_OK;
@@ -560,7 +560,7 @@ int32_t build_op_split(cosmo_hip_handle* h, bool any_a, bool fold, int factor_mi
   h->op_split = true;
   h->vm_am.swap(am_src); h->vm_ptm.swap(ptm_src);
   prp.resize((size_t)n + 1);
-  if (fold) CHK(fold_build(h, Am, prp, pcol, pval, factor_min));      // assembled operator where Am' rho Am is sparse enough (cg_fold.hip)
+  if (fold) CHK(fold_build(h, Am, prp, pcol, pval, factor_min, factor_fill_min));      // assembled operator where Am' rho Am is sparse enough (cg_fold.hip)
   return COSMO_HIP_OK;
 }
 

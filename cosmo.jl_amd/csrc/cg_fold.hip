@@ -112,12 +112,24 @@ __global__ __launch_bounds__(COSMO_BS) void k_fold_start(Ctl* __restrict__ ctl, 
 // longer single row takes the generic path).
 // PC: beta = rho_k / rho_{k-1} with rho = z'r from the second partial set (ctl->sr_gamma, by iteration parity: the single-reduction CG that
 // otherwise owns those two scalars is a different kkt_kind), u_k = z + beta u_{k-1} from the {z, u} records; the stopping rule stays ||r||_2.
-template <int SL, bool PC>
-__global__ __launch_bounds__(COSMO_BS) void k_cg_dirM(Ctl* __restrict__ ctl, int guard, int check_first, int k, long long n, long long maxiter,
+// PSM (pre-scattered dense rows, FoldPlan::ps_mode): >= 1: (Ad u_k) goes to the tile-major tcur (tpos); 2: every c_j is also stored at the slots of the
+// dense-row image where column j occurs (srec / sovf: static lists, the first-row record is requested with the row pointers), for k_cg_updF<2>.
+// k_cg_dirM<SL, PC> is the body with PSM = 0 (the assembled operator, the Jacobi recurrence, the CSR-stream factored form), k_cg_dirMs<SL, PSM> with PSM = 1 | 2.
+
+// v at every slot of column j (sr = its record {slot, slot, begin, end} of FoldPlan::ad_srec)
+__device__ __forceinline__ void ad_scatter(const int4 sr, const int* __restrict__ sovf, real* __restrict__ dst, real v) {
+  if (sr.x >= 0) dst[sr.x] = v;
+  if (sr.y >= 0) dst[sr.y] = v;
+  for (int s = sr.z; s < sr.w; ++s) dst[sovf[s]] = v;
+}
+
+template <int SL, bool PC, int PSM>
+__device__ __forceinline__ void cg_dirM_body(Ctl* __restrict__ ctl, int guard, int check_first, int k, long long n, long long maxiter,
                                                       const real* __restrict__ part_rr, int n_rr, CsrView M, const real2* __restrict__ ru,
                                                       real* __restrict__ c, real* __restrict__ u, real* __restrict__ part_uc,
                                                       const real* __restrict__ part_rz, const int* __restrict__ pcol, const real* __restrict__ pval,
-                                                      const real2* __restrict__ tt, real* __restrict__ tcur, int nd) {
+                                                      const real2* __restrict__ tt, real* __restrict__ tcur, int nd, const int* __restrict__ tpos,
+                                                      const int4* __restrict__ srec, const int* __restrict__ sovf, real* __restrict__ ad_c) {
   // partial assembly (FoldPlan::nd > 0): a column cc >= n of the stored matrix [Ms | Ad' rho_d] gathers the record tt[cc - n] = {(Ad r)_kd, (Ad u_prev)_kd}; the
   // rebuilt value x + beta y is then (Ad u_k)_kd, just as {r, u} gives u_k for the columns < n.  nd == 0: every column is < n and REC is ru[cc].
 #define REC(cc) (((cc) < (int)n) ? ru[(cc)] : tt[(cc) - (int)n])
@@ -171,6 +183,10 @@ __global__ __launch_bounds__(COSMO_BS) void k_cg_dirM(Ctl* __restrict__ ctl, int
   const real2 rw = ru[rr_];                                       // {r, u_{k-1}} of this thread's row: u_k of the row for u'c
   const long long i0 = (long long)blockIdx.x * COSMO_BS + threadIdx.x;
   const real2 own = ru[i0 < n ? i0 : 0];
+  int4 sr0 = make_int4(-1, -1, 0, 0);
+  int tp0 = 0;
+  if constexpr (PSM == 2) sr0 = srec[rr_];
+  if constexpr (PSM >= 1) tp0 = tpos[i0 < nd ? i0 : 0];
   if (guard && ctl->halt) return;
   if (ctl->cg_done) return;
   __shared__ real lds[COSMO_NNZ_PER_BLOCK];
@@ -201,7 +217,8 @@ __global__ __launch_bounds__(COSMO_BS) void k_cg_dirM(Ctl* __restrict__ ctl, int
   }
   for (long long kd = i0; kd < nd; kd += (long long)gridDim.x * COSMO_BS) {      // (Ad u_k) for the record k_cg_updF writes: the same expression the gathers evaluate
     const real2 v = tt[kd];
-    tcur[kd] = v.x + beta * v.y;
+    if constexpr (PSM >= 1) tcur[kd == i0 ? tp0 : tpos[kd]] = v.x + beta * v.y;
+    else tcur[kd] = v.x + beta * v.y;
   }
   real acc = 0.0;
   if (fast) {
@@ -214,12 +231,14 @@ __global__ __launch_bounds__(COSMO_BS) void k_cg_dirM(Ctl* __restrict__ ctl, int
     if (rowok) {                                    // first row of this thread: pointers and its own record already here
       const real cj = lds_seq_sum(lds, pa_ - d.z, pb_ - d.z);
       c[rfirst] = cj;
+      if constexpr (PSM == 2) ad_scatter(sr0, sovf, ad_c, cj);
       acc += (rw.x + beta * rw.y) * cj;
     }
     for (int r = rfirst + COSMO_BS; r < d.y; r += COSMO_BS) {
       const real cj = lds_seq_sum(lds, M.rowptr[r] - d.z, M.rowptr[r + 1] - d.z);
       const real2 v = ru[r];
       c[r] = cj;
+      if constexpr (PSM == 2) ad_scatter(srec[r], sovf, ad_c, cj);
       acc += (v.x + beta * v.y) * cj;
     }
     __syncthreads();
@@ -231,12 +250,31 @@ __global__ __launch_bounds__(COSMO_BS) void k_cg_dirM(Ctl* __restrict__ ctl, int
                         const real cj = s1 + s2;
                         const real2 v = ru[r];
                         c[r] = cj;
+                        if constexpr (PSM == 2) ad_scatter(srec[r], sovf, ad_c, cj);
                         acc += (v.x + beta * v.y) * cj;
                       });
   }
   acc = block_sum(acc, red);
   if (threadIdx.x == 0) part_uc[M.xcd_affine ? first_tile : (int)blockIdx.x] = acc;
 #undef REC
+}
+template <int SL, bool PC>
+__global__ __launch_bounds__(COSMO_BS) void k_cg_dirM(Ctl* __restrict__ ctl, int guard, int check_first, int k, long long n, long long maxiter,
+                                                      const real* __restrict__ part_rr, int n_rr, CsrView M, const real2* __restrict__ ru,
+                                                      real* __restrict__ c, real* __restrict__ u, real* __restrict__ part_uc,
+                                                      const real* __restrict__ part_rz, const int* __restrict__ pcol, const real* __restrict__ pval,
+                                                      const real2* __restrict__ tt, real* __restrict__ tcur, int nd) {
+  cg_dirM_body<SL, PC, 0>(ctl, guard, check_first, k, n, maxiter, part_rr, n_rr, M, ru, c, u, part_uc, part_rz, pcol, pval, tt, tcur, nd, nullptr, nullptr, nullptr, nullptr);
+}
+// ... on a partially assembled operator whose dense rows have the pre-scattered image (the literal recurrence only)
+template <int SL, int PSM>
+__global__ __launch_bounds__(COSMO_BS) void k_cg_dirMs(Ctl* __restrict__ ctl, int guard, int check_first, int k, long long n, long long maxiter,
+                                                       const real* __restrict__ part_rr, int n_rr, CsrView M, const real2* __restrict__ ru,
+                                                       real* __restrict__ c, real* __restrict__ u, real* __restrict__ part_uc,
+                                                       const int* __restrict__ pcol, const real* __restrict__ pval,
+                                                       const real2* __restrict__ tt, real* __restrict__ tcur, int nd, const int* __restrict__ tpos,
+                                                       const int4* __restrict__ srec, const int* __restrict__ sovf, real* __restrict__ ad_c) {
+  cg_dirM_body<SL, false, PSM>(ctl, guard, check_first, k, n, maxiter, part_rr, n_rr, M, ru, c, u, part_uc, nullptr, pcol, pval, tt, tcur, nd, tpos, srec, sovf, ad_c);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -247,17 +285,20 @@ __global__ __launch_bounds__(COSMO_BS) void k_cg_dirM(Ctl* __restrict__ ctl, int
 //                (Ad r_new) as a fresh CSR-stream product over the dense rows with r_new REBUILT at the gathered columns from the old (parity-buffered) records.
 // ---------------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(COSMO_BS) void k_ad_dot(const Ctl* __restrict__ ctl, int guard, CsrView Ad, const real* __restrict__ v, real* __restrict__ out,
-                                                     real2* __restrict__ out_rec) {
+                                                     real2* __restrict__ out_rec, const int* __restrict__ img_col, real* __restrict__ img_v, long long nimg) {
   if (guard && ctl->halt) return;
   __shared__ real lds[COSMO_NNZ_PER_BLOCK];
   __shared__ real red[COSMO_BS / 64];
   for (int t = blockIdx.x; t < Ad.nb; t += gridDim.x)
     csr_stream_tile(Ad, v, v, t, lds, red, [&](int kd, real s1, real s2) { if (out_rec) out_rec[kd] = make_real2(s1 + s2, R(0.0)); else out[kd] = s1 + s2; });
+  // pre-scattered operands (k_cg_updF<2>): v = r0 in slot order for iteration 0, whose owners (k_fold_start) do not know the slots (nimg == 0: none)
+  for (long long e = (long long)blockIdx.x * COSMO_BS + threadIdx.x; e < nimg; e += (long long)gridDim.x * COSMO_BS) img_v[e] = v[img_col[e]];
 }
 
 // ADSL: nonzero slots per thread of a dense-row tile (tiles of Ad hold at most ADSL * 256 nonzeros; a longer single row takes the generic path)
 #define ADSL 4
-__global__ __launch_bounds__(COSMO_BS) void k_cg_updF(Ctl* __restrict__ ctl, int guard, int k, long long n, const real* __restrict__ part_uc, int n_uc,
+// k_cg_updF0: the CSR-stream form (the reference of the pre-scattered k_cg_updF<PSM> below; COSMO_HIP_FOLD_PRESCATTER=0)
+__global__ __launch_bounds__(COSMO_BS) void k_cg_updF0(Ctl* __restrict__ ctl, int guard, int k, long long n, const real* __restrict__ part_uc, int n_uc,
                                                       const real* __restrict__ u, const real* __restrict__ c, real* __restrict__ x, real* __restrict__ r,
                                                       real* __restrict__ part_rr, const real2* __restrict__ ru_old, real2* __restrict__ ru_new, int gE, int nd,
                                                       CsrView Ad, real2* __restrict__ tt, const real* __restrict__ tcur) {
@@ -354,6 +395,126 @@ __global__ __launch_bounds__(COSMO_BS) void k_cg_updF(Ctl* __restrict__ ctl, int
   }
 }
 
+// k_cg_updF<PSM>: k_cg_updF0 on the PRE-SCATTERED image of the dense rows (FoldPlan::ps_mode; profiles/cg_fold_prescatter.txt).  The same arithmetic, expression by expression
+// (COSMO_HIP_FOLD_PRESCATTER=0 keeps k_cg_updF0 as the reference: tests/test_gpu_cg_fold_prescatter.py compares the two bit for bit); what changes is where the
+// operands of a dense-tile workgroup's FIRST tile come from: values, local row pointers, (Ad u_k) of the tile's rows (tile-major tcur) and -- PSM == 2 -- r_j and
+// c_j themselves sit at addresses that depend on the block index alone, so the whole tile is ONE batch of loads next to the u'c partials and the control block
+// (k_cg_updF0: descriptor -> (col, val, rowptr, tcur) -> gathers, three dependent trips through the fabric in a kernel whose other workgroups need one).
+// PSM == 1 keeps the gathers behind the image's columns (two trips).  PSM == 2: the owners of r store r_new at the slots of their column for the NEXT parity
+// (ad_rn), as k_cg_dirM<.., 2> does for c; ad_c needs no second buffer (the next k_cg_dirM starts after this kernel has ended).  The control block's scalars
+// (both parities of resv) are requested with everything else instead of behind the flags.  Tiles beyond a workgroup's first and single rows longer than a
+// tile take the generic path on Ad's CSR arrays, as in k_cg_updF0.
+template <int PSM>
+__global__ __launch_bounds__(COSMO_BS) void k_cg_updF(Ctl* __restrict__ ctl, int guard, int k, long long n, const real* __restrict__ part_uc, int n_uc,
+                                                      const real* __restrict__ u, const real* __restrict__ c, real* __restrict__ x, real* __restrict__ r,
+                                                      real* __restrict__ part_rr, const real2* __restrict__ ru_old, real2* __restrict__ ru_new, int gE, int nd,
+                                                      CsrView Ad, real2* __restrict__ tt, const real* __restrict__ tcur, const int* __restrict__ tpos,
+                                                      const int* __restrict__ icol, const real* __restrict__ iav, const int* __restrict__ lrp,
+                                                      const int4* __restrict__ srec, const int* __restrict__ sovf, const real* __restrict__ ad_c,
+                                                      const real* __restrict__ ad_rc, real* __restrict__ ad_rn) {
+  __shared__ real lds[COSMO_NNZ_PER_BLOCK];
+  __shared__ real red[COSMO_BS / 64];
+  if ((int)blockIdx.x < gE) {
+    // ---- workgroups [0, gE): the vector update of k_cg_upd<false>, r_old taken from the old records ------------------------------------------------
+    const long long i0 = (long long)blockIdx.x * COSMO_BS + threadIdx.x;
+    const long long i0c = i0 < n ? i0 : 0;
+    const real u0 = u[i0c], c0 = c[i0c], x0 = x[i0c], r0 = ru_old[i0c].x;
+    int4 sr0 = make_int4(-1, -1, 0, 0);
+    if constexpr (PSM == 2) sr0 = srec[i0c];
+    const real pa = partials_prefetch_sum(part_uc, n_uc);
+    const int halt = ctl->halt, cdone = ctl->cg_done, kd_ = ctl->cg_kd;
+    const real rv0 = ctl->resv[0], rv1 = ctl->resv[1];
+    if (guard && halt) return;
+    if (cdone) return;
+    if (k < 0) k = kd_;
+    const real res = (k & 1) ? rv1 : rv0;
+    const real uc = block_sum(pa, red);
+    const real alpha = (res * res) / uc;
+    real acc = 0.0;
+    if (i0 < n) {
+      x[i0] = x0 + alpha * u0;
+      const real ri = r0 - alpha * c0;
+      r[i0] = ri;
+      ru_new[i0] = make_real2(ri, u0);
+      if constexpr (PSM == 2) ad_scatter(sr0, sovf, ad_rn, ri);
+      acc += ri * ri;
+    }
+    for (long long i = i0 + (long long)gE * COSMO_BS; i < n; i += (long long)gE * COSMO_BS) {
+      const real ui = u[i];
+      x[i] = x[i] + alpha * ui;
+      const real ri = ru_old[i].x - alpha * c[i];
+      r[i] = ri;
+      ru_new[i] = make_real2(ri, ui);
+      if constexpr (PSM == 2) ad_scatter(srec[i], sovf, ad_rn, ri);
+      acc += ri * ri;
+    }
+    acc = block_sum(acc, red);
+    if (threadIdx.x == 0) {
+      part_rr[blockIdx.x] = acc;
+      if (blockIdx.x == 0) ctl->cg_k = k + 1;
+    }
+    return;
+  }
+  // ---- workgroups [gE, ...): tiles of the dense rows; every address below is a function of the block index (the host builds the image for the first tile of
+  // every workgroup: first_tile < FoldPlan::ad_nt) --------------------------------------------------------------------------------------------------------
+  const int first_tile = (int)blockIdx.x - gE;
+  const bool have_tile = first_tile < Ad.nb;
+  const int ft = have_tile ? first_tile : 0;
+  const int4 d = reinterpret_cast<const int4*>(Ad.rb)[ft];
+  real av[ADSL], gr[ADSL], gc[ADSL];
+  if constexpr (PSM == 2) {
+#pragma unroll
+    for (int it = 0; it < ADSL; ++it) {
+      const long long e = (long long)ft * (ADSL * COSMO_BS) + it * COSMO_BS + threadIdx.x;
+      av[it] = iav[e]; gr[it] = ad_rc[e]; gc[it] = ad_c[e];
+    }
+  } else {
+    int ccs[ADSL];
+#pragma unroll
+    for (int it = 0; it < ADSL; ++it) {
+      const long long e = (long long)ft * (ADSL * COSMO_BS) + it * COSMO_BS + threadIdx.x;
+      ccs[it] = icol[e]; av[it] = iav[e];
+    }
+#pragma unroll
+    for (int it = 0; it < ADSL; ++it) { gr[it] = ru_old[ccs[it]].x; gc[it] = c[ccs[it]]; }
+  }
+  const int pa_ = lrp[ft * (COSMO_BS + 1) + threadIdx.x], pb_ = lrp[ft * (COSMO_BS + 1) + threadIdx.x + 1];
+  const real tk_ = tcur[(long long)ft * COSMO_BS + threadIdx.x];
+  const real pa = partials_prefetch_sum(part_uc, n_uc);
+  const int halt = ctl->halt, cdone = ctl->cg_done, kd_ = ctl->cg_kd;
+  const real rv0 = ctl->resv[0], rv1 = ctl->resv[1];
+  if (guard && halt) return;
+  if (cdone) return;
+  if (k < 0) k = kd_;
+  const real res = (k & 1) ? rv1 : rv0;
+  const int cnt0 = d.w - d.z;
+  const bool fast = have_tile && cnt0 <= ADSL * COSMO_BS;
+  const int rfirst = d.x + threadIdx.x;
+  const bool rowok = fast && rfirst < d.y;
+  const real uc = block_sum(pa, red);
+  const real alpha = (res * res) / uc;
+  if (fast) {                                       // a tile has at most 256 rows (build_row_blocks: ROWS_MAX of a tile below COSMO_NNZ_PER_BLOCK): one row per thread
+#pragma unroll
+    for (int it = 0; it < ADSL; ++it) {
+      const int kk = it * COSMO_BS + threadIdx.x;
+      if (kk < cnt0) lds[kk] = av[it] * (gr[it] - alpha * gc[it]);
+    }
+    __syncthreads();
+    if (rowok) tt[rfirst] = make_real2(lds_seq_sum(lds, pa_, pb_), tk_);
+    __syncthreads();
+  }
+  for (int t = fast ? first_tile + ((int)gridDim.x - gE) : first_tile; t < Ad.nb; t += (int)gridDim.x - gE) {
+    const int4 dd = reinterpret_cast<const int4*>(Ad.rb)[t];
+    csr_stream_rows_g(Ad, [&](int cc) { return ru_old[cc].x - alpha * c[cc]; }, dd.x, dd.y, dd.z, dd.w, lds, red,
+                      [&](int kd, real s1, real s2) { tt[kd] = make_real2(s1 + s2, tcur[tpos[kd]]); });
+  }
+}
+
+// the padded values follow Ad.val (cosmo_hip_update_matrices)
+__global__ __launch_bounds__(COSMO_BS) void k_ad_image_vals(long long nnz, const int* __restrict__ pos, const real* __restrict__ val, real* __restrict__ iav) {
+  for (long long p = (long long)blockIdx.x * COSMO_BS + threadIdx.x; p < nnz; p += (long long)gridDim.x * COSMO_BS) { const int q = pos[p]; if (q >= 0) iav[q] = val[p]; }
+}
+
 // ---------------------------------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------------------------------
@@ -377,7 +538,16 @@ void fold_free(cosmo_hip_handle* h) {
   if (f->tt) (void)hipFree(f->tt);
   if (f->tcur) (void)hipFree(f->tcur);
   if (f->tx) (void)hipFree(f->tx);
-  if (f->chain) (void)hipGraphExecDestroy((hipGraphExec_t)f->chain);
+  if (f->ad_col) (void)hipFree(f->ad_col);
+  if (f->ad_av) (void)hipFree(f->ad_av);
+  if (f->ad_lrp) (void)hipFree(f->ad_lrp);
+  if (f->ad_pos) (void)hipFree(f->ad_pos);
+  if (f->ad_tpos) (void)hipFree(f->ad_tpos);
+  if (f->ad_srec) (void)hipFree(f->ad_srec);
+  if (f->ad_sovf) (void)hipFree(f->ad_sovf);
+  if (f->ad_c) (void)hipFree(f->ad_c);
+  if (f->ad_r) (void)hipFree(f->ad_r);
+  if (f->chain)(void)hipGraphExecDestroy((hipGraphExec_t)f->chain);
   if (f->chain_cf) (void)hipGraphExecDestroy((hipGraphExec_t)f->chain_cf);
   if (f->sr_chain) (void)hipGraphExecDestroy((hipGraphExec_t)f->sr_chain);
   if (f->sr_chain_cf) (void)hipGraphExecDestroy((hipGraphExec_t)f->sr_chain_cf);
@@ -395,7 +565,7 @@ static int32_t up(cosmo_hip_handle* h, T** dst, const std::vector<T>& v) {
 // Am: the multi-nonzero rows of A (compact, columns ascending within a row); (prp, pcol, pval): CSR of P.  Called at the end of
 // build_op_split (the split is active and rho_m / diag exist on the device).
 int32_t fold_build(cosmo_hip_handle* h, const HostCsr& Am, const std::vector<int>& prp, const std::vector<int>& pcol,
-                   const std::vector<real>& pval, int factor_min) {
+                   const std::vector<real>& pval, int factor_min, long long factor_fill_min) {
   fold_free(h);
   if (h->n <= 0) return COSMO_HIP_OK;
   const long long n = h->n;
@@ -413,14 +583,17 @@ int32_t fold_build(cosmo_hip_handle* h, const HostCsr& Am, const std::vector<int
   // the 708 k entries of M; partially assembled 107 k + 60 k).  MEASURED (profiles/r06_partial_assembly.txt): k_cg_dirM 7.7 -> 4.9 us -- it is then at the
   // floor of a kernel of this chain, k_cg_upd<false> with next to no data takes the same 4.9 us -- but k_cg_updF 4.9 -> 6.2 us (the dense rows' own
   // col -> gather chain sits BEHIND alpha); per Krylov iteration as the loop enqueues it 11.72 -> 11.30 us, 250.9 -> 253.9 it/s (+1.2 %): below what it costs in
-  // code paths, hence OPT-IN (COSMO_HIP_FOLD_FACTOR=1; COSMO_HIP_FOLD_FACTOR_MIN=len moves the row-length threshold; kkt.hip: factor_min).  The literal
-  // recurrence only.
+  // code paths, hence opt-in THEN (COSMO_HIP_FOLD_FACTOR=1; COSMO_HIP_FOLD_FACTOR_MIN=len moves the row-length threshold; kkt.hip: factor_min).  The literal
+  // recurrence only.  With the PRE-SCATTERED image of the dense rows (below; profiles/cg_fold_prescatter.txt) the update kernel needs one round trip like its
+  // vector half: 11.79 -> 10.81 us per Krylov iteration, 246.0 -> 253.3 it/s on config 5, and the form is the DEFAULT where it avoids enough fill (kkt.hip).
   std::vector<int> did((size_t)mm, -1);
   int nd = 0;
   if (factor_min > 0) {
-    long long part = 0, dense_nnz = 0;
-    for (int r = 0; r < mm; ++r) { const long long len = Am.rowptr[r + 1] - Am.rowptr[r]; if (len >= factor_min) { dense_nnz += len; } else part += len * len; }
-    if (dense_nnz > 0 && 2 * (part + 2 * dense_nnz) <= nterms)
+    // factor_fill_min (the DEFAULT rule, kkt.hip; 0 when COSMO_HIP_FOLD_FACTOR=1 forces the form): the fill that factoring avoids, sum of len^2 over the
+    // factored rows minus the 2 len entries they keep, must reach it -- below, the assembled pair is as fast and the operator stays one matrix
+    long long part = 0, dense_nnz = 0, avoided = 0;
+    for (int r = 0; r < mm; ++r) { const long long len = Am.rowptr[r + 1] - Am.rowptr[r]; if (len >= factor_min) { dense_nnz += len; avoided += len * len - 2 * len; } else part += len * len; }
+    if (dense_nnz > 0 && 2 * (part + 2 * dense_nnz) <= nterms && avoided >= factor_fill_min)
       for (int r = 0; r < mm; ++r) if (Am.rowptr[r + 1] - Am.rowptr[r] >= factor_min) did[(size_t)r] = nd++;
   }
   // Am' as lists (row of Am, value) per column
@@ -514,6 +687,58 @@ int32_t fold_build(cosmo_hip_handle* h, const HostCsr& Am, const std::vector<int
     HIPCHK(h, hipMalloc((void**)&f->tcur, sizeof(real) * (size_t)nd));
     HIPCHK(h, hipMalloc((void**)&f->tx, sizeof(real) * (size_t)nd));
     HIPCHK(h, hipMemset(f->tt, 0, sizeof(real2) * (size_t)nd)); HIPCHK(h, hipMemset(f->tcur, 0, sizeof(real) * (size_t)nd)); HIPCHK(h, hipMemset(f->tx, 0, sizeof(real) * (size_t)nd));
+    // PRE-SCATTERED image (k_cg_updF; default where rows stay factored, COSMO_HIP_FOLD_PRESCATTER=0: the CSR-stream form k_cg_updF0, =2: lab, the image without
+    // the slot-ordered operands).  Entry order within a row and the partition into tiles are those of Ad's CSR-stream schedule (the same build_row_blocks call
+    // as upload_csr); only the first tile of every workgroup gets an image, and a single row longer than a tile none.
+    int mode = 2;
+    if (const char* e = getenv("COSMO_HIP_FOLD_PRESCATTER")) { const int v = atoi(e); mode = v == 0 ? 0 : v == 2 ? 1 : 2; }
+    std::vector<int> rbnd;
+    build_row_blocks(Adh.rowptr, nd, rbnd, ADSL * COSMO_BS);
+    const size_t nbk = rbnd.size() - 1;
+    const int cap = ADSL * COSMO_BS;
+    const size_t nt = std::min<size_t>(nbk, (size_t)std::max(f->Ad.grid, 1));
+    bool fits = (long long)nbk == f->Ad.nb && nbk >= 1 && nbk * (size_t)COSMO_BS < ((size_t)1 << 30);
+    for (size_t k = 0; fits && k < nbk; ++k) fits = rbnd[k + 1] - rbnd[k] <= COSMO_BS;
+    if (mode != 0 && fits) {
+      std::vector<int> icol(nt * cap, 0), lrp(nt * (COSMO_BS + 1), 0), pos(Adh.col.size(), -1), tpos((size_t)nd, 0);
+      std::vector<real> iav(nt * cap, R(0.0));
+      for (size_t k = 0; k < nbk; ++k)
+        for (int r = rbnd[k]; r < rbnd[k + 1]; ++r) tpos[(size_t)r] = (int)(k * COSMO_BS) + (r - rbnd[k]);
+      for (size_t k = 0; k < nt; ++k) {
+        const int r0 = rbnd[k], r1 = rbnd[k + 1], z0 = Adh.rowptr[r0], z1 = Adh.rowptr[r1];
+        if (z1 - z0 > cap) continue;                                // generic path: the image holds padding only
+        for (int e2 = z0; e2 < z1; ++e2) { const size_t q = k * cap + (size_t)(e2 - z0); icol[q] = Adh.col[e2]; iav[q] = Adh.val[e2]; pos[(size_t)e2] = (int)q; }
+        for (int i = 0; i <= COSMO_BS; ++i) lrp[k * (COSMO_BS + 1) + i] = (r0 + i <= r1) ? Adh.rowptr[r0 + i] - z0 : z1 - z0;
+      }
+      // the inverse map: for column j the slots where it occurs, ascending (a CSC of the padded layout; the first two in the column's record)
+      std::vector<int> cnt((size_t)n, 0), srec((size_t)n * 4, 0), sovf;
+      for (size_t j = 0; j < (size_t)n; ++j) { srec[4 * j] = -1; srec[4 * j + 1] = -1; }
+      std::vector<std::vector<int>> more;
+      std::vector<int> more_of((size_t)n, -1);
+      for (size_t e2 = 0; e2 < pos.size(); ++e2) {
+        if (pos[e2] < 0) continue;
+        const size_t j = (size_t)Adh.col[e2];
+        if (cnt[j] < 2) srec[4 * j + cnt[j]] = pos[e2];
+        else { if (more_of[j] < 0) { more_of[j] = (int)more.size(); more.emplace_back(); } more[(size_t)more_of[j]].push_back(pos[e2]); }
+        cnt[j]++;
+      }
+      for (size_t j = 0; j < (size_t)n; ++j) {
+        srec[4 * j + 2] = (int)sovf.size();
+        if (more_of[j] >= 0) sovf.insert(sovf.end(), more[(size_t)more_of[j]].begin(), more[(size_t)more_of[j]].end());
+        srec[4 * j + 3] = (int)sovf.size();
+      }
+      CHK(up(h, &f->ad_col, icol)); CHK(up(h, &f->ad_av, iav)); CHK(up(h, &f->ad_lrp, lrp)); CHK(up(h, &f->ad_pos, pos)); CHK(up(h, &f->ad_tpos, tpos));
+      (void)hipFree(f->tcur); f->tcur = nullptr;                    // tile-major: 256 rows per tile
+      HIPCHK(h, hipMalloc((void**)&f->tcur, sizeof(real) * nbk * COSMO_BS));
+      HIPCHK(h, hipMemset(f->tcur, 0, sizeof(real) * nbk * COSMO_BS));
+      if (mode == 2) {
+        CHK(up(h, &f->ad_srec, srec)); CHK(up(h, &f->ad_sovf, sovf));
+        HIPCHK(h, hipMalloc((void**)&f->ad_c, sizeof(real) * nt * cap));
+        HIPCHK(h, hipMalloc((void**)&f->ad_r, sizeof(real) * 2 * nt * cap));
+        HIPCHK(h, hipMemset(f->ad_c, 0, sizeof(real) * nt * cap)); HIPCHK(h, hipMemset(f->ad_r, 0, sizeof(real) * 2 * nt * cap));
+      }
+      f->ps_mode = mode; f->ad_nt = (int)nt; f->ad_cap = cap;
+    }
   }
   // Tile size: measured on BASELINE config 5 (708 k nonzeros; profiles/r02_cfg5_fold_tile_sweep.txt) 256 / 384 / 512 / 768 / 1408
   // nonzeros per tile all land within +-2 % (144-150 it/s): the kernel is a chain of dependent round trips, not a stream.  768 keeps
@@ -568,20 +793,30 @@ int32_t fold_refresh(cosmo_hip_handle* h) {
   return COSMO_HIP_OK;
 }
 
+int32_t fold_ad_image_refresh(cosmo_hip_handle* h) {
+  FoldPlan* f = (FoldPlan*)h->fold;
+  if (!h->op_fold || !f || f->ps_mode == 0 || f->Ad.nnz <= 0) return COSMO_HIP_OK;
+  hipLaunchKernelGGL(k_ad_image_vals, dim3(ew_grid(f->Ad.nnz)), dim3(COSMO_BS), 0, h->stream, f->Ad.nnz, (const int*)f->ad_pos, (const real*)f->Ad.val, f->ad_av);
+  HIPCHK(h, hipGetLastError());
+  return COSMO_HIP_OK;
+}
+
 int32_t fold_enqueue_start(cosmo_hip_handle* h, int guard, real tol_k) {
   FoldPlan* f = (FoldPlan*)h->fold;
   const int gD = f->nd > 0 ? std::max(f->Ad.grid, 1) : 0;
   prof_begin(h, KC_OP_APPLY);
   if (f->nd > 0)               // partial assembly: (Ad x) for the start residual r0 = rhs - (Ms x + Ad' rho (Ad x))
-    hipLaunchKernelGGL(k_ad_dot, dim3(gD), dim3(COSMO_BS), 0, h->stream, h->ctl, guard, view_of(f->Ad), (const real*)h->x_tl, f->tx, (real2*)nullptr);
+    hipLaunchKernelGGL(k_ad_dot, dim3(gD), dim3(COSMO_BS), 0, h->stream, h->ctl, guard, view_of(f->Ad), (const real*)h->x_tl, f->tx, (real2*)nullptr,
+                       (const int*)nullptr, (real*)nullptr, 0LL);
   if (h->route == KKT_CG_JACOBI)
     hipLaunchKernelGGL(k_fold_start<true>, dim3(f->M.grid), dim3(COSMO_BS), 0, h->stream, h->ctl, guard, view_of(f->M), h->x_tl, h->rhs, h->r,
                        (real2*)h->cg_ru, PARTS(h, SLOT_RR), PARTS(h, SLOT_BB), h->n_bb, tol_k, (const real*)f->dinv, PARTS(h, SLOT_AUX2), (const real*)nullptr);
   else
     hipLaunchKernelGGL(k_fold_start<false>, dim3(f->M.grid), dim3(COSMO_BS), 0, h->stream, h->ctl, guard, view_of(f->M), h->x_tl, h->rhs, h->r,
                        (real2*)h->cg_ru, PARTS(h, SLOT_RR), PARTS(h, SLOT_BB), h->n_bb, tol_k, (const real*)nullptr, (real*)nullptr, (const real*)(f->nd > 0 ? f->tx : nullptr));
-  if (f->nd > 0)               // ... and the records {Ad r0, 0} of iteration 0
-    hipLaunchKernelGGL(k_ad_dot, dim3(gD), dim3(COSMO_BS), 0, h->stream, h->ctl, guard, view_of(f->Ad), (const real*)h->r, (real*)nullptr, f->tt);
+  if (f->nd > 0)               // ... and the records {Ad r0, 0} of iteration 0 (pre-scattered operands: r0 in slot order for parity 0)
+    hipLaunchKernelGGL(k_ad_dot, dim3(gD), dim3(COSMO_BS), 0, h->stream, h->ctl, guard, view_of(f->Ad), (const real*)h->r, (real*)nullptr, f->tt,
+                       (const int*)f->ad_col, f->ad_r, f->ps_mode == 2 ? (long long)f->ad_nt * f->ad_cap : 0LL);
   prof_end(h);
   h->spmv_calls[0] += 1; h->spmv_calls[1] += 2; h->spmv_calls[2] += 1;     // the reference's multiplication count (A' y2 of the rhs + reduced_mul! = A, A', P)
   HIPCHK(h, hipGetLastError());
@@ -599,7 +834,12 @@ static void fold_launch_pair(cosmo_hip_handle* h, FoldPlan* f, int guard, int k,
 #define LAUNCH_DIRM_(SLN, PCF) hipLaunchKernelGGL((k_cg_dirM<SLN, PCF>), dim3(f->M.grid), dim3(COSMO_BS), 0, h->stream, h->ctl, guard, check_first, k, n, n, \
                          PARTS(h, SLOT_RR), n_rr, view_of(f->M), ru_cur, h->c, h->u, PARTS(h, SLOT_UC), (const real*)PARTS(h, SLOT_AUX2), \
                          (const int*)(f->cap == SLN * COSMO_BS ? f->pcol : nullptr), (const real*)f->pval, (const real2*)f->tt, f->tcur, f->nd)
-#define LAUNCH_DIRM(SLN) do { if (h->route == KKT_CG_JACOBI) LAUNCH_DIRM_(SLN, true); else LAUNCH_DIRM_(SLN, false); } while (0)
+#define LAUNCH_DIRMS_(SLN, PSM) hipLaunchKernelGGL((k_cg_dirMs<SLN, PSM>), dim3(f->M.grid), dim3(COSMO_BS), 0, h->stream, h->ctl, guard, check_first, k, n, n, \
+                         PARTS(h, SLOT_RR), n_rr, view_of(f->M), ru_cur, h->c, h->u, PARTS(h, SLOT_UC), \
+                         (const int*)(f->cap == SLN * COSMO_BS ? f->pcol : nullptr), (const real*)f->pval, (const real2*)f->tt, f->tcur, f->nd, \
+                         (const int*)f->ad_tpos, (const int4*)f->ad_srec, (const int*)f->ad_sovf, f->ad_c)
+#define LAUNCH_DIRM(SLN) do { if (h->route == KKT_CG_JACOBI) LAUNCH_DIRM_(SLN, true); else if (f->ps_mode == 2) LAUNCH_DIRMS_(SLN, 2); \
+                              else if (f->ps_mode == 1) LAUNCH_DIRMS_(SLN, 1); else LAUNCH_DIRM_(SLN, false); } while (0)
   switch (f->slots) {
     case 1: LAUNCH_DIRM(1); break;
     case 2: LAUNCH_DIRM(2); break;
@@ -609,11 +849,21 @@ static void fold_launch_pair(cosmo_hip_handle* h, FoldPlan* f, int guard, int k,
   }
 #undef LAUNCH_DIRM
 #undef LAUNCH_DIRM_
+#undef LAUNCH_DIRMS_
   prof_end(h);
   if (f->nd > 0) {             // partial assembly: the vector update + the linear update of (Ad r) on the dense rows (workgroups behind the first gE)
     const int gE = ew_grid(n), gD = std::max(f->Ad.grid, 1);
     prof_begin(h, KC_CG_UPD);
-    hipLaunchKernelGGL(k_cg_updF, dim3(gE + gD), dim3(COSMO_BS), 0, h->stream, h->ctl, guard, k, n, PARTS(h, SLOT_UC), f->M.grid, h->u, h->c, h->x_tl, h->r, PARTS(h, SLOT_RR),
+    if (f->ps_mode != 0) {       // the pre-scattered image: r in slot order alternates by parity like the records
+      const size_t nimg = (size_t)f->ad_nt * f->ad_cap;
+#define LAUNCH_UPDF(PSM) hipLaunchKernelGGL(k_cg_updF<PSM>, dim3(gE + gD), dim3(COSMO_BS), 0, h->stream, h->ctl, guard, k, n, PARTS(h, SLOT_UC), f->M.grid, h->u, h->c, h->x_tl, \
+                       h->r, PARTS(h, SLOT_RR), ru_cur, ru_nxt, gE, f->nd, view_of(f->Ad), f->tt, (const real*)f->tcur, (const int*)f->ad_tpos, (const int*)f->ad_col, \
+                       (const real*)f->ad_av, (const int*)f->ad_lrp, (const int4*)f->ad_srec, (const int*)f->ad_sovf, (const real*)f->ad_c, \
+                       (const real*)(f->ad_r ? f->ad_r + (size_t)par * nimg : nullptr), f->ad_r ? f->ad_r + (size_t)(par ^ 1) * nimg : (real*)nullptr)
+      if (f->ps_mode == 2) LAUNCH_UPDF(2); else LAUNCH_UPDF(1);
+#undef LAUNCH_UPDF
+    } else
+    hipLaunchKernelGGL(k_cg_updF0, dim3(gE + gD), dim3(COSMO_BS), 0, h->stream, h->ctl, guard, k, n, PARTS(h, SLOT_UC), f->M.grid, h->u, h->c, h->x_tl, h->r, PARTS(h, SLOT_RR),
                        ru_cur, ru_nxt, gE, f->nd, view_of(f->Ad), f->tt, (const real*)f->tcur);
     prof_end(h);
   } else (void)launch_cg_upd(h, guard, k, f->M.grid);

@@ -124,6 +124,21 @@ struct FoldPlan {
   real2* tt = nullptr;    // nd records {Ad r, Ad u_prev}
   real* tcur = nullptr;   // nd: Ad u of the iteration in flight (written by k_cg_dirM, stored into the record by k_cg_updF)
   real* tx = nullptr;     // nd: Ad x (solve start)
+  // PRE-SCATTERED dense rows (cg_fold.hip: k_cg_updF<1 | 2>; COSMO_HIP_FOLD_PRESCATTER): a tile-major padded image of Ad's first-pass tiles (ad_cap slots per
+  // tile, like pcol / pval for M) with the operands the tiles gather -- r_j and c_j -- kept IN SLOT ORDER by the kernels that write r and c, so that every
+  // address a dense-tile workgroup needs depends on its block index alone (one memory round trip instead of descriptor -> columns -> gathers)
+  int ps_mode = 0;          // 0: the CSR-stream form; 1: image of (col, val, row pointers, tcur) only; 2: image + pre-scattered operands
+  int ad_nt = 0;            // tiles in the image: the first tile of every dense-row workgroup (a longer-than-cap single row is declined: no slots)
+  int ad_cap = 0;           // slots per tile (ADSL * 256)
+  int* ad_col = nullptr;    // ad_nt * ad_cap (padding: column 0)
+  real* ad_av = nullptr;  // ad_nt * ad_cap (padding: 0)
+  int* ad_lrp = nullptr;    // ad_nt * 257: row pointers of the tile's rows relative to its first nonzero (absent rows: the tile's count)
+  int* ad_pos = nullptr;    // nnz(Ad): slot of entry p, -1 outside the image (update_matrices refills ad_av through it)
+  int* ad_tpos = nullptr;   // nd: position of row kd in the tile-major tcur (tile * 256 + row within the tile)
+  int* ad_srec = nullptr;   // 4 ints per column j < n, {slot, slot, begin, end}: the first two slots where column j occurs (-1: none), the others are ad_sovf[begin .. end)
+  int* ad_sovf = nullptr;
+  real* ad_c = nullptr;   // ad_nt * ad_cap: c_j of the iteration in flight at the slots of column j (written by k_cg_dirM)
+  real* ad_r = nullptr;   // 2 * ad_nt * ad_cap: r_j at the slots of column j, by iteration parity like the {r, u} records
   // the same for the one-launch single-reduction recurrence (cg_sr.hip: k_sr_M); chain_len is even there (records / partials alternate by parity)
   void* sr_chain = nullptr;
   void* sr_chain_cf = nullptr;
@@ -338,7 +353,7 @@ int32_t feedback_record(cosmo_hip_handle* h);                   // its Krylov co
 
 // CG operator split (api.hip); any_a: build the split for any A (row sharding), fold: assemble it where sparse enough (cg_fold.hip),
 // keeping the rows of A with >= factor_min nonzeros factored (0: none)
-int32_t build_op_split(cosmo_hip_handle* h, bool any_a, bool fold, int factor_min);
+int32_t build_op_split(cosmo_hip_handle* h, bool any_a, bool fold, int factor_min, long long factor_fill_min);
 int32_t refresh_op_split(cosmo_hip_handle* h);   // kernels.hip
 void free_op_split(cosmo_hip_handle* h);
 
@@ -386,8 +401,9 @@ int32_t time_op_apply(cosmo_hip_handle* h, int reps, double* avg_seconds);
 
 // assembled reduced operator (cg_fold.hip)
 int32_t fold_build(cosmo_hip_handle* h, const HostCsr& Am, const std::vector<int>& prp, const std::vector<int>& pcol,
-                   const std::vector<real>& pval, int factor_min);
+                   const std::vector<real>& pval, int factor_min, long long factor_fill_min);
 int32_t fold_refresh(cosmo_hip_handle* h);
+int32_t fold_ad_image_refresh(cosmo_hip_handle* h);            // Ad.val has new values (update_matrices): the padded image follows
 void fold_free(cosmo_hip_handle* h);
 int32_t fold_enqueue_start(cosmo_hip_handle* h, int guard, real tol_k);
 int32_t fold_enqueue_iterations(cosmo_hip_handle* h, int guard, int k_begin, int count);

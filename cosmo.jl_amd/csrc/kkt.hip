@@ -7,6 +7,9 @@
 #include <algorithm>
 #include "internal.h"
 
+// Default rule of the partial assembly (profiles/cg_fold_prescatter.txt): sum over the rows that would stay factored of len^2 - 2 len
+#define FOLD_FACTOR_FILL_DEFAULT 300000LL
+
 static int env_int(const char* name, int dflt) {
   const char* e = getenv(name);
   return e ? atoi(e) : dflt;
@@ -32,7 +35,9 @@ void kkt_free(cosmo_hip_handle* h) {
 //   COSMO_HIP_OP_FOLD=0        no assembled operator
 //   COSMO_HIP_CG_FUSE_DIR=0    the four-launch literal recurrence (k_cg_dirA needs the {r, u} records, which the assembled operator gathers too)
 //   COSMO_HIP_CG_PERSIST=1     the persistent single-launch CG where the operator fits it (the split operator stays unassembled)
-//   COSMO_HIP_FOLD_FACTOR=1    partial assembly: rows of A with >= COSMO_HIP_FOLD_FACTOR_MIN (4) nonzeros stay factored (literal recurrence only)
+//   COSMO_HIP_FOLD_FACTOR=0|1  partial assembly off / forced: rows of A with >= COSMO_HIP_FOLD_FACTOR_MIN (4) nonzeros stay factored (literal recurrence
+//                              only).  Unset: factored where that avoids at least COSMO_HIP_FOLD_FACTOR_FILL (FOLD_FACTOR_FILL_DEFAULT) assembled entries
+//   COSMO_HIP_FOLD_PRESCATTER=0  factored rows: the CSR-stream update kernel k_cg_updF0 instead of the pre-scattered image (read in cg_fold.hip: fold_build)
 //   COSMO_HIP_CG_SR_DEFAULT=1  lab switch: kkt_kind CG on a fully assembled operator runs the one-launch single-reduction recurrence
 // force_split (set_row_shard): h->A becomes a row slice, so the reduced operator must be the split form of the WHOLE A, for any A; the persistent
 // kernel, whose operands are sized for the unsharded handle, gives way to the multi-kernel loop.  Everything else of the route stays.
@@ -43,9 +48,16 @@ int32_t kkt_configure(cosmo_hip_handle* h, bool force_split) {
   const bool fold = !env_zero("COSMO_HIP_OP_FOLD");
   const bool fuse = env_int("COSMO_HIP_CG_FUSE_DIR", 1) != 0;
   const bool persist = env_int("COSMO_HIP_CG_PERSIST", 0) != 0;
+  // partial assembly: forced either way by COSMO_HIP_FOLD_FACTOR; unset, the rows stay factored where the fill that avoids reaches FOLD_FACTOR_FILL_DEFAULT
+  // (decided once per plan from the row lengths of A; cg_fold.hip: fold_build)
   int factor_min = 0;
-  if (kind == COSMO_HIP_KKT_CG && env_int("COSMO_HIP_FOLD_FACTOR", 0) != 0) { factor_min = env_int("COSMO_HIP_FOLD_FACTOR_MIN", 4); if (factor_min < 2) factor_min = 4; }
+  long long factor_fill_min = 0;
+  if (kind == COSMO_HIP_KKT_CG && !env_zero("COSMO_HIP_FOLD_FACTOR")) {
+    factor_min = env_int("COSMO_HIP_FOLD_FACTOR_MIN", 4); if (factor_min < 2) factor_min = 4;
+    if (env_int("COSMO_HIP_FOLD_FACTOR", 0) == 0) { factor_fill_min = FOLD_FACTOR_FILL_DEFAULT; if (const char* e = getenv("COSMO_HIP_FOLD_FACTOR_FILL")) factor_fill_min = atoll(e); }
+  }
   const bool sr_default = env_int("COSMO_HIP_CG_SR_DEFAULT", 0) != 0;
+  if (sr_default && factor_fill_min > 0) factor_min = 0;      // the lab switch asks for the fully assembled operator; only a forced factoring overrides it
   if (force_split) {
     if (h->route == KKT_CG_PERSIST) { pcg_free(h); h->route = literal_route(h); }
     if (h->op_split) return COSMO_HIP_OK;
@@ -70,7 +82,7 @@ int32_t kkt_configure(cosmo_hip_handle* h, bool force_split) {
   // enough for the recurrences that gather records -- {r, u} of the fused literal pair, {r, w, s, p} of the single-reduction one
   bool sr = kind == COSMO_HIP_KKT_CG_SR;
   if (split && (cg || (force_split && kind == COSMO_HIP_KKT_MINRES_REDUCED)))
-    CHK(build_op_split(h, force_split, cg && fold && !persist && (sr || h->cg_ru), factor_min));
+    CHK(build_op_split(h, force_split, cg && fold && !persist && (sr || h->cg_ru), factor_min, factor_fill_min));
   // LAB SWITCH (COSMO_HIP_CG_SR_DEFAULT=1; round 6): kkt_kind CG on an ASSEMBLED reduced operator runs the one-launch
   // single-reduction recurrence (cg_sr.hip: k_sr_M) instead of the literal pair.  Measured as a candidate default and REJECTED (BASELINE config 5:
   // 12.42 vs 11.50 us per Krylov iteration -- the 24-byte gathers of {r, w, s} from 32-byte records cost more than the launch they save, every
@@ -287,7 +299,9 @@ extern "C" const char* cosmo_hip_kkt_recurrence(cosmo_hip_handle* h) {
       return buf;
     case KKT_CG_SR: return "cg: single-reduction recurrence, two launches per iteration (kkt_kind CG_SR), k_sr_update_A + k_sr_op";
     case KKT_CG_FOLD_PARTIAL:
-      snprintf(buf, sizeof buf, "cg: literal recurrence on the partially assembled operator (%d rows of A kept factored), two launches per iteration, %s", f->nd, updf_names[sl]);
+      snprintf(buf, sizeof buf, "cg: literal recurrence on the partially assembled operator (%d rows of A kept factored), two launches per iteration, %s%s", f->nd, updf_names[sl],
+               f->ps_mode == 2 ? "" : f->ps_mode == 1 ? " (dense-row image without pre-scattered operands, COSMO_HIP_FOLD_PRESCATTER=2)"
+                                                      : " (CSR-stream dense rows k_cg_updF0, COSMO_HIP_FOLD_PRESCATTER=0)");      // default: k_cg_dirMs<SL, 2> + k_cg_updF<2>
       return buf;
     case KKT_CG_FOLD: snprintf(buf, sizeof buf, "cg: literal recurrence on the assembled operator, two launches per iteration, %s", pair_names[sl]); return buf;
     case KKT_CG_FUSED: return "cg: literal recurrence, three launches per iteration, k_cg_dirA + k_op_apply + k_cg_upd<false>";

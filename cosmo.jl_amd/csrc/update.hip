@@ -126,7 +126,7 @@ int32_t upd_refresh_operator(cosmo_hip_handle* h) {
     if (f->nterms > 0) hipLaunchKernelGGL(k_upd_tprod, dim3(egrid(f->nterms)), dim3(COSMO_BS), 0, st, f->nterms, (const int*)f->u_ta, (const int*)f->u_tb, (const real*)h->Am.val, f->tprod);
     if (f->M.nnz > 0) hipLaunchKernelGGL(k_upd_base, dim3(egrid(f->M.nnz)), dim3(COSMO_BS), 0, st, f->M.nnz, (const int*)f->u_bptr, (const int*)f->u_bsrc, (const real*)h->P.val, f->base);
     h->upd_refreshed += 2;
-    if (f->nd > 0) { copy_pass(h, f->Ad, f->u_ad, h->Am.val, nullptr, INT32_MAX, 0, nullptr, nullptr, nullptr, R(1.0)); h->upd_refreshed += 1; }
+    if (f->nd > 0) { copy_pass(h, f->Ad, f->u_ad, h->Am.val, nullptr, INT32_MAX, 0, nullptr, nullptr, nullptr, R(1.0)); CHK(fold_ad_image_refresh(h)); h->upd_refreshed += 1; }
   }
   HIPCHK(h, hipGetLastError());
   return COSMO_HIP_OK;
