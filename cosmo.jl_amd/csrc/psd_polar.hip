@@ -39,7 +39,11 @@
 // v_mfma_f64_16x16x4_f64 accumulators), k-panels of 16 staged through double-buffered LDS with an 80-real row pitch
 // (conflict-free ds_read_b64 for the 16-lane x 4-row operand fragments), global loads of panel k+1 in flight during
 // the MFMAs of panel k.
+//
+// Which tiles a product consists of -- tile side and k-split of a large cone, the quadrant, ragged and paired tile lists of the batch and their order --
+// is planned by host-only code, polar_tiles.h / polar_tiles.cpp; this file reads the knobs, uploads the lists and runs the kernels on them.
 #include "psd_internal.h"
+#include "polar_tiles.h"
 #include <math.h>
 #include <stdlib.h>
 #include <string.h>
@@ -52,18 +56,8 @@
                                  // (167.8 vs 167.4 us per product), slower in the batched kernel (51.1 vs 47.5 us): profiles/r02_prefetch_depth.txt
 #endif
 #define PLD 80  // LDS row pitch in doubles
-
-struct PolarCone {
-  int idx;            // index in PsdPlan::cones
-  int off, d, kind;
-  int ts;             // tile side of the products (64 or 96), chosen per cone
-  int sk;             // 2: intra-workgroup split of k (8 waves), when the upper tiles give at most one tile per CU; 3: stream-K
-  int skg, skc;       // stream-K: workgroups of a launch, ticket classes (8 = one tile range per XCD, 1 = a single range)
-  int ld;             // d rounded up to ts
-  long long woff;     // offset of this cone's 4 work matrices (doubles)
-};
-
-struct BatchCone { long long woff; int off, d, kind, ld, idx, ts; };   // a mid-size cone of the batched path (device table); ts = tile side of its products (64 | 96)
+static_assert(PK == kPolarPanelK, "the planner's k panel");
+static_assert(sizeof(QTile) == sizeof(int4), "the quadrant list is uploaded as the kernels' int4 array");
 
 // device-side control of the verification / fallback rounds (one per plan; the large cones are projected one after the other)
 // stream-K product (k_symm_gemm_sk): ticket counter, spin-timeout marker, flag[G] = epoch of the slot's last partial tile
@@ -94,6 +88,7 @@ static const real kPolarFinish[POLAR_NFIN][3] = {
 #define POLAR_NFIN_LARGE (REAL_IS_FLOAT ? 4 : POLAR_NFIN)
 #define POLAR_RLIFT_LARGE (REAL_IS_FLOAT ? 4 : POLAR_RLIFT)
 
+#define POLAR_LIFT_CAP 18
 struct PolarPlan {
   std::vector<PolarCone> cones;
   real* W = nullptr;       // 4 * ld^2 doubles per cone: X, U, Y, T
@@ -105,6 +100,7 @@ struct PolarPlan {
   // iterates of a convergent run need 11-12, where the grow-by-3 rule of polar_adapt takes over as it did from 10).  Float32: 5 -- the verification threshold 8 d eps scales with eps(Float32) (2e-4 ... 2e-3 for
   // d = 200 ... 2000), eigenvalues below it pass by construction, and 0.0425 * 3.84^-5 = 5e-5 is already beneath it
   int k_lift = REAL_IS_FLOAT ? 5 : 9;
+  bool klift_forced = false; // COSMO_HIP_POLAR_KLIFT was set when the plan was created: the depth stays what it says
   int max_rounds = 2;        // guarded fallback rounds enqueued per projection
   int rescale = 1;           // spectral rescaling in the first step of a large cone's iteration (COSMO_HIP_POLAR_RESCALE=0 disables)
   int batch_occ = 3;         // register-allocation variant of the batched product kernels: 3 or 4 waves per SIMD (COSMO_HIP_POLAR_BATCH_OCC; the plan sets 4 for the ragged kernel)
@@ -170,9 +166,9 @@ struct PolarPlan {
   real* bnrm = nullptr;    // per batched cone ||X||_F
   int* bgate = nullptr;      // per batched cone: 1 = its verification failed, the next fallback round processes it
   // ---- per-cone lifting depth of the batch (round 4) ------------------------------------------------------------------------------------
-  // Every cone of the batch runs ITS OWN number of lifting steps bk[c] (cone c joins the batch's schedule at step kmax - bk[c]: the gate table
-  // lgate[t * n + c] = (t >= kmax - bk[c]) is handed to the product kernels as the per-cone gate they already have for the fallback rounds) and
-  // the depth follows the cone's own verification history: bk[c] - 1 after `bm[c]` consecutive verified projections, bk[c] + 1 (and the cone
+  // Every cone of the batch runs ITS OWN number of lifting steps k_c = bdepth[c].k (cone c joins the batch's schedule at step kmax - k_c: the gate table
+  // lgate[t * n + c] = (t >= kmax - k_c) is handed to the product kernels as the per-cone gate they already have for the fallback rounds) and
+  // the depth follows the cone's own verification history (LiftDepth): k_c - 1 after `patience` consecutive verified projections, k_c + 1 (and the cone
   // alone takes a fallback round, as before) on a failed verification, after which the cone waits twice as long before it probes downwards
   // again.  The a-posteriori check is unchanged, so the error bound of every projection is the same rigorous 8 d eps ||X||_F.  Replay on the
   // spectra of BASELINE config 5 (tests/studies/lift_depth_replay.py, profiles/r04_lift_depth_replay.txt): minimal passing depth 3-5 for
@@ -187,18 +183,20 @@ struct PolarPlan {
   // 128.8 vs 129.0 it/s.
   int adapt = 0;
   int compact_repair = 1;                // COSMO_HIP_POLAR_COMPACT_REPAIR=0: the full-grid gated repair train of round 4
-  std::vector<int> bk, bstreak, bm;     // per batched cone: lifting depth, verified projections since the last change, patience
+  std::vector<LiftDepth> bdepth;        // per batched cone: lifting depth, verified projections since the last change, patience
   int* d_lgate = nullptr;                // (LIFT_CAP x n) gate table of the lifting steps
   int* d_ubuf = nullptr;                 // per cone: work buffer (1 | 2) that receives U_0 (the one that is `iu` when the cone joins)
   int* bgate_host = nullptr;             // pinned: per-cone verification result of round 0
   int lgate_kmax = -1;                   // kmax the device tables were built for (-1: dirty)
   long long depth_fail = 0, depth_down = 0, depth_proj = 0;
   int seen_proj_batch = 0;               // PolarDev::projections at the last depth-control step
-  std::vector<int> lk, lstreak, lm;      // the same control per LARGE cone (one cone per projection: the depth is simply its main schedule)
+  std::vector<LiftDepth> ldepth;         // the same control per LARGE cone (one cone per projection: the depth is simply its main schedule)
   int seen_proj_large = 0;
   double wprod_last = 0.0;               // sum_c d_c^3 * products of cone c / sum_c d_c^3 of the last projection (main schedule + verification)
+  // adaptive per-cone depth needs the per-cone verification results on the host: not in speculative mode (no synchronisation inside a projection),
+  // not with a schedule forced through COSMO_HIP_POLAR_KLIFT
+  bool adaptive() const { return adapt && !speculate && !klift_forced && k_lift <= POLAR_LIFT_CAP; }
 };
-#define POLAR_LIFT_CAP 18
 
 extern "C" int32_t cosmo_hip_polar_schedule(int32_t k_lift, double* abc, int32_t* nsteps) {
   if (k_lift < 0 || k_lift > 64 || !nsteps) return COSMO_HIP_ERR_INVALID;
@@ -589,6 +587,7 @@ __global__ __launch_bounds__(256 * SK) void k_symm_gemm(const Ctl* __restrict__ 
 //    order them) and read with agent-scope loads -- correct wherever the workgroups were placed, and without the L2 write-back /
 //    invalidate of a release / acquire fence pair (which costs every other workgroup of the XCD its cached panels).
 #define SKG_TS 96
+static_assert(SKG_TS == kPolarStreamKTile, "the planner's stream-K tile side");
 
 template <int EPI>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) void k_symm_gemm_sk(const Ctl* __restrict__ ctl, int guard, const int* __restrict__ gate, const real* __restrict__ A,
@@ -720,10 +719,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(OCC, OCC)))
 // the parts are chosen), the epilogue is the same LDS transposition restricted to the tile's extents.
 // ext = ei | ej << 8 | diag << 16 (ei, ej in blocks of 16).  The descriptor carries everything the kernel needs from the cone (ld, side, offset
 // of its work matrices): one 32-byte load instead of descriptor -> cone table -> operands, i.e. one dependent round trip to memory less in a
-// prologue that the in-kernel clocks (tools/ragged_timing_lab.py) put at 21 % of a tile's life.
-struct alignas(32) RTile { int cone; int i0, j0; int ext; int ld, d; long long woff; };
+// prologue that the in-kernel clocks (tools/ragged_timing_lab.py) put at 21 % of a tile's life.  (RTile: polar_tiles.h)
 
-#ifdef POLAR_LAB_TIMING       // lab instrumentation (tools/build_lab_variants.sh TIMING): shader-clock cycles of wave 0 of every workgroup, summed per phase
+#ifdef POLAR_LAB_TIMING      // lab instrumentation (tools/build_lab_variants.sh TIMING): shader-clock cycles of wave 0 of every workgroup, summed per phase
 #define RT_MAXT 8192
 __device__ unsigned long long g_rt[RT_MAXT * 5];     // per workgroup of the LAST launch: start, first panel in LDS, end of main loop, end, k-panels (plain stores: atomics
                                                       // on shared counters serialised 9 k tile ends and doubled the kernel time)
@@ -1053,8 +1051,7 @@ __device__ __forceinline__ unsigned df_ld(const unsigned* p) { return __hip_atom
 // What pairing along the rows leaves over lies in the LAST block column (row I has P - I tiles): by default (COSMO_HIP_POLAR_PAIRED=3; 1: rows only) those
 // tiles (I, P - 1), (I', P - 1) ride in one item too and share the column's B panel (profiles/polar_paired_tiles.txt: rows -2.2...-4.0 %, both -3.3 % of the launch).  The kernel does not know which kind of item it runs: it stages the DISTINCT panels
 // among {A of tile 0, B of tile 0, A of tile 1, B of tile 1} -- at most three by construction of the list -- and each half reads its fragments from the
-// images of its two.
-struct alignas(16) RPair { int cone; int i0, j0, i1, j1; int ext0, ext1; int ld, d; int pad; long long woff; };
+// images of its two.  (RPair: polar_tiles.h)
 
 // Main loop of an item: the DEPTH = 1 pipeline of symm_mainloop_r on np <= 3 panels (np, off[]: workgroup-uniform).  aimg / bimg: the LDS images (stage 0)
 // this wave reads its A / B fragments from.
@@ -1664,66 +1661,110 @@ void polar_plan_destroy(cosmo_hip_handle* h) {
 
 bool polar_enabled(const cosmo_hip_handle* h) { return h->psd_polar != nullptr; }
 
-// called by psd_plan_create once the Jacobi plan (which owns the cone list) exists
+// ---- knobs of plan creation --------------------------------------------------------------------------------------------------------------------------
+// Every environment variable that plan creation reads is read here, each with its meaning (what it costs or buys is written at the PolarPlan member it
+// sets and at the kernels).  -1: not set, the plan decides.
+struct PolarKnobs {
+  int large_jacobi = -1, k_lift = -1, adapt = 0, compact_repair = 1, rescale = 1, speculate = -1, rounds = -1, patience = 3;
+  int streamk = 0, ts = 0, sk = 0;
+  long long skg = 0;
+  int ts96 = 0, wave = 0, flat = 0, ragged = 1, paired = -1, sort = 1, dataflow = -1, dataflow_grid = -1, occ = -1;
+};
+
+static PolarKnobs polar_read_knobs() {
+  PolarKnobs k;
+  auto flag = [](const char* name, int dflt) { const char* e = getenv(name); return e ? (atoi(e) ? 1 : 0) : dflt; };
+  auto within = [](const char* name, int lo, int hi, int dflt) { const char* e = getenv(name); const int v = e ? atoi(e) : dflt; return (v >= lo && v <= hi) ? v : dflt; };
+  if (const char* e = getenv("COSMO_HIP_PSD_LARGE")) k.large_jacobi = (e[0] == 'j') ? 1 : 0;                 // "jacobi": keep the host-paced Jacobi path for real large cones
+  if (const char* e = getenv("COSMO_HIP_POLAR_KLIFT")) k.k_lift = std::min(40, std::max(0, atoi(e)));       // lifting steps of the main schedule, FORCED: no adaptation afterwards
+  k.adapt = flag("COSMO_HIP_POLAR_ADAPT", k.adapt);                                                         // 1: per-cone lifting depth
+  if (const char* e = getenv("COSMO_HIP_POLAR_PATIENCE")) k.patience = std::max(1, atoi(e));                // ... verified projections before a batched cone probes one step down
+  k.compact_repair = flag("COSMO_HIP_POLAR_COMPACT_REPAIR", k.compact_repair);                              // 0: full-grid gated repair train
+  k.rescale = flag("COSMO_HIP_POLAR_RESCALE", k.rescale);                                                   // 0: no spectral rescaling in a large cone's first step
+  k.speculate = flag("COSMO_HIP_POLAR_SPECULATE", k.speculate);                                             // fallback rounds always enqueued behind device-side gates (default: from three large cones on)
+  if (const char* e = getenv("COSMO_HIP_POLAR_ROUNDS")) k.rounds = std::min(8, std::max(0, atoi(e)));       // guarded fallback rounds per projection
+  k.streamk = flag("COSMO_HIP_POLAR_STREAMK", k.streamk);                                                   // 1: stream-K product kernel for the large cones
+  if (const char* e = getenv("COSMO_HIP_POLAR_TS")) k.ts = atoi(e);                                         // 64 | 96: tile side of the large cones
+  if (const char* e = getenv("COSMO_HIP_POLAR_SK")) k.sk = atoi(e);                                         // 1 | 2: their k-split
+  if (const char* e = getenv("COSMO_HIP_POLAR_SKG")) k.skg = atoll(e);                                      // workgroups of a stream-K launch
+  k.ts96 = flag("COSMO_HIP_POLAR_BATCH_TS96", k.ts96);                                                      // 1: 96 x 96 tile class in the batch (implies the quadrant kernel)
+  k.wave = flag("COSMO_HIP_POLAR_BATCH_WAVE", k.wave);                                                      // 1: wave-per-tile kernel for the 64 x 64 class (implies the quadrant kernel)
+  k.flat = getenv("COSMO_HIP_POLAR_BATCH_FLAT") ? 1 : 0;                                                    // set at all: quadrant list in cone order, no XCD interleaving
+  k.ragged = flag("COSMO_HIP_POLAR_BATCH_RAGGED", k.ragged);                                                // 0: the 64 x 64 quadrant kernel
+  k.sort = flag("COSMO_HIP_POLAR_BATCH_SORT", k.sort);                                                      // 0: ragged tiles in cone order instead of decreasing modelled cost
+  k.occ = within("COSMO_HIP_POLAR_BATCH_OCC", 3, 4, k.occ);                                                 // waves per SIMD of the batched product kernels (default: 4 ragged, 3 quadrant)
+  k.paired = within("COSMO_HIP_POLAR_PAIRED", 0, 3, k.paired);                                              // form of the persistent launch's queue items (PolarPlan::df_pair)
+  k.dataflow = flag("COSMO_HIP_POLAR_DATAFLOW", k.dataflow);                                                // persistent dependency-driven main schedule of the batch (default: by the batch's size)
+  k.dataflow_grid = within("COSMO_HIP_POLAR_DATAFLOW_GRID", 8, 8192, k.dataflow_grid);                      // ... its workgroups (default: four per CU)
+  return k;
+}
+
+// dynamic LDS of the batched product kernels
+static void polar_set_func_attributes(const PolarPlan* q) {
+  if (q->bcones.empty()) return;
+  if (q->batch_ragged) {
+    (void)hipFuncSetAttribute((const void*)k_polar_dataflow<4>, hipFuncAttributeMaxDynamicSharedMemorySize, GemmCfg<64>::SMEM);
+    (void)hipFuncSetAttribute((const void*)k_polar_dataflow_pair<4>, hipFuncAttributeMaxDynamicSharedMemorySize, DF_PAIR_SMEM);
+    (void)hipFuncSetAttribute((const void*)k_symm_gemm_batch_r<0, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, GemmCfg<64>::SMEM);
+    (void)hipFuncSetAttribute((const void*)k_symm_gemm_batch_r<1, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, GemmCfg<64>::SMEM);
+    (void)hipFuncSetAttribute((const void*)k_symm_gemm_batch_r<0, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, GemmCfg<64>::SMEM);
+    (void)hipFuncSetAttribute((const void*)k_symm_gemm_batch_r<1, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, GemmCfg<64>::SMEM);
+  }
+  (void)hipFuncSetAttribute((const void*)k_symm_gemm_batch<0, 3, 64>, hipFuncAttributeMaxDynamicSharedMemorySize, GemmCfg<64>::SMEM);
+  (void)hipFuncSetAttribute((const void*)k_symm_gemm_batch<1, 3, 64>, hipFuncAttributeMaxDynamicSharedMemorySize, GemmCfg<64>::SMEM);
+  (void)hipFuncSetAttribute((const void*)k_symm_gemm_batch<0, 4, 64>, hipFuncAttributeMaxDynamicSharedMemorySize, GemmCfg<64>::SMEM);
+  (void)hipFuncSetAttribute((const void*)k_symm_gemm_batch<1, 4, 64>, hipFuncAttributeMaxDynamicSharedMemorySize, GemmCfg<64>::SMEM);
+  (void)hipFuncSetAttribute((const void*)k_symm_gemm_batch<0, 2, 96>, hipFuncAttributeMaxDynamicSharedMemorySize, GemmCfg<96>::SMEM);
+  (void)hipFuncSetAttribute((const void*)k_symm_gemm_batch<1, 2, 96>, hipFuncAttributeMaxDynamicSharedMemorySize, GemmCfg<96>::SMEM);
+}
+
+// device copy of a host array
+template <class T>
+static int32_t polar_upload(cosmo_hip_handle* h, T** dst, const void* src, size_t bytes) {
+  HIPCHK(h, hipMalloc((void**)dst, bytes));
+  HIPCHK(h, hipMemcpy(*dst, src, bytes, hipMemcpyHostToDevice));
+  return COSMO_HIP_OK;
+}
+
+// called by psd_plan_create once the Jacobi plan (which owns the cone list) exists: read the knobs, plan the tiles (polar_tiles.cpp), allocate and
+// upload, set the kernels' attributes
 int32_t polar_plan_create(cosmo_hip_handle* h) {
   polar_plan_destroy(h);
   PsdPlan* p = h->psd;
   if (!p) return COSMO_HIP_OK;
+  const PolarKnobs k = polar_read_knobs();
   std::vector<int> large_list, batch_list = p->polar_batch;
-  bool jac = h->psd_mode == 1;                                                        // cosmo_hip_set_psd_projection(EIGEN)
-  if (const char* e = getenv("COSMO_HIP_PSD_LARGE")) jac = (e[0] == 'j');            // "jacobi": keep the host-paced Jacobi path for real cones
+  const bool jac = k.large_jacobi >= 0 ? k.large_jacobi == 1 : h->psd_mode == 1;      // cosmo_hip_set_psd_projection(EIGEN)
   if (!jac) large_list = p->large;
   p->large_by_polar = !jac;
   for (int idx : p->cplx) { if (p->cones[idx].d > 256) large_list.push_back(idx); else batch_list.push_back(idx); }
-  const bool use_large = !large_list.empty(), use_batch = !batch_list.empty();
-  if (!use_large && !use_batch) return COSMO_HIP_OK;
+  if (large_list.empty() && batch_list.empty()) return COSMO_HIP_OK;
   PolarPlan* q = new PolarPlan();
   h->psd_polar = q;
-  if (const char* e = getenv("COSMO_HIP_POLAR_KLIFT")) q->k_lift = std::min(40, std::max(0, atoi(e)));
-  if (const char* e = getenv("COSMO_HIP_POLAR_ADAPT")) q->adapt = atoi(e) ? 1 : 0;
-  if (const char* e = getenv("COSMO_HIP_POLAR_COMPACT_REPAIR")) q->compact_repair = atoi(e) ? 1 : 0;
-  if (const char* e = getenv("COSMO_HIP_POLAR_RESCALE")) q->rescale = atoi(e) ? 1 : 0;
-  if (const char* e = getenv("COSMO_HIP_POLAR_STREAMK")) q->streamk = atoi(e) ? 1 : 0;
-  if (const char* e = getenv("COSMO_HIP_POLAR_BATCH_TS96")) q->batch_ts96 = atoi(e) ? 1 : 0;
-  if (const char* e = getenv("COSMO_HIP_POLAR_BATCH_WAVE")) q->batch_wave = atoi(e) ? 1 : 0;
-  q->speculate = (large_list.size() > 2) ? 1 : 0;          // many large cones: no pipeline drain per cone (see the header)
-  if (const char* e = getenv("COSMO_HIP_POLAR_SPECULATE")) q->speculate = atoi(e) ? 1 : 0;
+  q->klift_forced = k.k_lift >= 0;
+  if (q->klift_forced) q->k_lift = k.k_lift;
+  q->adapt = k.adapt; q->compact_repair = k.compact_repair; q->rescale = k.rescale; q->streamk = k.streamk;
+  q->batch_ts96 = k.ts96; q->batch_wave = k.wave;
+  q->speculate = k.speculate >= 0 ? k.speculate : (large_list.size() > 2 ? 1 : 0);          // many large cones: no pipeline drain per cone (see the header)
+  if (k.rounds >= 0) q->max_rounds = k.rounds;
+  q->batch_ragged = (k.ragged && !k.ts96 && !k.wave) ? 1 : 0;
+  if (k.paired >= 0) q->df_pair = k.paired;
+  PolarTileOpts o;
+  o.ts96 = k.ts96; o.flat = k.flat; o.ragged = q->batch_ragged; o.pair = q->df_pair; o.sort = k.sort;
+  o.streamk = k.streamk; o.ts = k.ts; o.sk = k.sk; o.skg = k.skg;
   HIPCHK(h, hipHostMalloc((void**)&q->gate_host, 8 * sizeof(int), hipHostMallocDefault));     // {gate, rounds, verified, unverified, projections} of PolarDev
   for (int i = 0; i < 8; ++i) q->gate_host[i] = 0;
-  if (const char* e = getenv("COSMO_HIP_POLAR_ROUNDS")) q->max_rounds = std::min(8, std::max(0, atoi(e)));
   HIPCHK(h, hipMalloc((void**)&q->dev, sizeof(PolarDev)));
   HIPCHK(h, hipMemset(q->dev, 0, sizeof(PolarDev)));
   memset(&q->seen, 0, sizeof(PolarDev));
-  if (use_large) {
+  if (!large_list.empty()) {
     long long woff = 0;
     for (int idx : large_list) {
       const PsdConeDev& c = p->cones[idx];
       PolarCone pc;
       pc.idx = idx; pc.off = c.off; pc.d = c.d; pc.kind = c.kind;
-      // tile side: minimise (rounds of upper tiles over the 256 CUs) x (tile work)
-      long long best = -1; pc.ts = 64;
-      for (int ts : {64, 96}) {
-        const long long nt = (c.d + ts - 1) / ts, tiles = nt * (nt + 1) / 2;
-        const long long cost = ((tiles + 255) / 256) * (long long)ts * ts;
-        if (best < 0 || cost < best) { best = cost; pc.ts = ts; }
-      }
-      if (const char* e = getenv("COSMO_HIP_POLAR_TS")) { const int v = atoi(e); if (v == 64 || v == 96) pc.ts = v; }
-      pc.ld = ((c.d + pc.ts - 1) / pc.ts) * pc.ts;
-      { const long long nt = pc.ld / pc.ts; pc.sk = (pc.ts == 96 && nt * (nt + 1) / 2 <= 256) ? 2 : 1; }
-      if (const char* e = getenv("COSMO_HIP_POLAR_SK")) { const int v = atoi(e); if (v == 1 || (v == 2 && pc.ts == 96)) pc.sk = v; }
-      pc.skg = 0; pc.skc = 8;
-      if (q->streamk) {
-        // stream-K: tiles of 96 whatever the count (quantisation no longer matters); 2 workgroups per CU when the cone has the work
-        pc.ts = SKG_TS; pc.sk = 3;
-        pc.ld = ((c.d + pc.ts - 1) / pc.ts) * pc.ts;
-        const long long nt = pc.ld / pc.ts, tiles = nt * (nt + 1) / 2, nk = pc.ld / PK;
-        pc.skc = tiles >= 64 ? 8 : 1;
-        const long long units_min = (tiles / pc.skc) * nk;                 // units of the smallest class
-        long long per = std::min<long long>(512 / pc.skc, std::max<long long>(1, units_min / 4));   // >= 4 panels per workgroup
-        if (const char* e = getenv("COSMO_HIP_POLAR_SKG")) { const long long v = atoll(e) / pc.skc; if (v >= 1 && v <= 1024 / pc.skc) per = std::min(v, std::max<long long>(1, units_min)); }
-        pc.skg = (int)(per * pc.skc);
-        q->sk_gmax = std::max(q->sk_gmax, pc.skg);
-      }
+      polar_plan_large(o, pc);
+      q->sk_gmax = std::max(q->sk_gmax, pc.skg);
       pc.woff = woff;
       woff += 4LL * pc.ld * pc.ld;
       q->cones.push_back(pc);
@@ -1739,225 +1780,68 @@ int32_t polar_plan_create(cosmo_hip_handle* h) {
       HIPCHK(h, hipMemset(q->sk_sync, 0, sb));
     }
   }
-  if (use_batch) {
-    long long woff = 0;
-    std::vector<int4> tiles;
-    for (int idx : batch_list) {
-      const PsdConeDev& c = p->cones[idx];
-      BatchCone bc;
-      bc.off = c.off; bc.d = c.d; bc.kind = c.kind; bc.idx = idx;
-      // tile side (opt-in, see PolarPlan::batch_ts96): 96 x 96 tiles stream 1.5x fewer operand bytes per flop than 64 x 64 tiles (12 vs 8
-      // flop per byte) and spend fewer barriers per flop; they would be used where they do not cost padding: sides in (64, 96] (one tile instead of three) and in
-      // (128, 192] (three tiles instead of six).  Everything else keeps 64 x 64 tiles.
-      bc.ts = (q->batch_ts96 && ((c.d > 64 && c.d <= 96) || (c.d > 128 && c.d <= 192))) ? 96 : 64;
-      bc.ld = ((c.d + bc.ts - 1) / bc.ts) * bc.ts;
-      bc.woff = woff;
-      woff += 4LL * bc.ld * bc.ld;
-      q->bcones.push_back(bc);
-    }
-    // longest k first: the tiles of the biggest cones start at once, the small ones fill the tail
-    std::vector<int> order(q->bcones.size());
-    for (size_t i = 0; i < order.size(); ++i) order[i] = (int)i;
-    std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return q->bcones[a].ld > q->bcones[b].ld; });
-    // XCD-aware order: workgroup b runs on XCD b % 8 and each XCD has its own L2, so all tiles of a cone go to ONE XCD (they
-    // share the cone's operand panels: 1.5-2.5x fewer HBM reads than tiles scattered over eight L2s); the cones are dealt to the
-    // XCD with the least work so far, descriptor 8 * slot + x is the slot-th tile of XCD x, short lists end with null tiles.
-    // One list per tile class (64, then 96): a product is one launch per class.
-    int count[2] = {0, 0};
-    for (int cls = 0; cls < 2; ++cls) {
-      const int ts = cls == 0 ? 64 : 96;
-      std::vector<int4> tl;
-      if (getenv("COSMO_HIP_POLAR_BATCH_FLAT")) {
-        for (int ci : order) {
-          if (q->bcones[ci].ts != ts) continue;
-          const int nt = q->bcones[ci].ld / ts;
-          for (int tj = 0; tj < nt; ++tj) for (int ti = 0; ti <= tj; ++ti) tl.push_back(int4{ci, ti, tj, 0});
-        }
-      } else {
-        std::vector<std::vector<int4>> xl(8);
-        long long load[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-        for (int ci : order) {
-          if (q->bcones[ci].ts != ts) continue;
-          const int nt = q->bcones[ci].ld / ts;
-          int x = 0;
-          for (int t = 1; t < 8; ++t) if (load[t] < load[x]) x = t;
-          for (int tj = 0; tj < nt; ++tj) for (int ti = 0; ti <= tj; ++ti) xl[x].push_back(int4{ci, ti, tj, 0});
-          load[x] += (long long)nt * (nt + 1) / 2 * q->bcones[ci].ld;
-        }
-        size_t maxlen = 0;
-        for (int x = 0; x < 8; ++x) maxlen = std::max(maxlen, xl[x].size());
-        tl.assign(8 * maxlen, int4{-1, 0, 0, 0});
-        for (int x = 0; x < 8; ++x) for (size_t sl = 0; sl < xl[x].size(); ++sl) tl[8 * sl + x] = xl[x][sl];
-      }
-      count[cls] = (int)tl.size();
-      tiles.insert(tiles.end(), tl.begin(), tl.end());
-    }
-    q->nbtiles = count[0]; q->nbtiles96 = count[1];
-    // ragged tile list (see k_symm_gemm_batch_r): a cone's side in blocks of 16, cut into ceil(nb16 / 4) nearly equal parts
-    if (const char* e = getenv("COSMO_HIP_POLAR_BATCH_RAGGED")) q->batch_ragged = atoi(e) ? 1 : 0;
-    if (q->batch_ts96 || q->batch_wave) q->batch_ragged = 0;
-    q->batch_flops_performed = q->batch_flops_useful = 0.0;
-    for (const BatchCone& bc : q->bcones) q->batch_flops_useful += (double)bc.d * bc.d * (bc.d + 1.0);
+  if (!batch_list.empty()) {
+    std::vector<PolarBatchIn> in;
+    for (int idx : batch_list) { const PsdConeDev& c = p->cones[idx]; in.push_back(PolarBatchIn{c.d, c.off, c.kind, idx}); }
+    PolarBatchPlan bp;
+    if (const char* err = polar_plan_batch(in, o, bp)) return cosmo_fail(h, COSMO_HIP_ERR_INVALID, err);
+    const size_t nb = bp.cones.size();
+    q->bcones = bp.cones;
+    q->nbtiles = bp.nbtiles; q->nbtiles96 = bp.nbtiles96;
+    q->batch_flops_performed = bp.flops_performed; q->batch_flops_useful = bp.flops_useful;
     if (q->batch_ragged) {
-      std::vector<std::vector<RTile>> xl(8);
-      std::vector<std::vector<RPair>> xp(8);       // the items of the persistent launch's 512-thread form
-      if (const char* e = getenv("COSMO_HIP_POLAR_PAIRED")) { const int v = atoi(e); if (v >= 0 && v <= 3) q->df_pair = v; }
-      long long load[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-      for (int ci : order) {
-        const BatchCone& bc = q->bcones[ci];
-        const int nb16 = (bc.d + 15) / 16, nt = (nb16 + 3) / 4;
-        std::vector<int> start(nt + 1, 0);
-        for (int t = 0; t < nt; ++t) start[t + 1] = start[t] + nb16 / nt + (t < nb16 % nt ? 1 : 0);   // larger parts first: i0 + 64 <= ld for every tile
-        int x = 0;
-        for (int t = 1; t < 8; ++t) if (load[t] < load[x]) x = t;
-        for (int tj = 0; tj < nt; ++tj)
-          for (int ti = 0; ti <= tj; ++ti) {
-            const int ei = start[ti + 1] - start[ti], ej = start[tj + 1] - start[tj], dg = (ti == tj) ? 1 : 0;
-            RTile rt; rt.cone = ci; rt.i0 = 16 * start[ti]; rt.j0 = 16 * start[tj]; rt.ext = ei | (ej << 8) | (dg << 16);
-            rt.ld = bc.ld; rt.d = bc.d; rt.woff = bc.woff;
-            if (rt.i0 + 64 > bc.ld || rt.j0 + 64 > bc.ld) return cosmo_fail(h, COSMO_HIP_ERR_INVALID, "ragged tile exceeds the leading dimension");
-            xl[x].push_back(rt);
-            const int nblk = dg ? ei * (ei + 1) / 2 : ei * ej, slots = (nblk + 3) / 4;
-            load[x] += (long long)slots * nb16;
-            q->batch_flops_performed += 2.0 * 256.0 * nblk * 16.0 * nb16;
-          }
-        // items: along block row ti the tiles (ti, ti), (ti, ti + 1), ... are taken two at a time -- diagonal + right neighbour, then off-diagonal neighbours;
-        // an odd one is left single.  What is left lies in the last block column: df_pair == 3 takes those tiles two at a time as well (they share the
-        // column's B panel).  df_pair == 2 (lab): every tile single, in the order of the tile list above
-        auto item = [&](int ti, int tj, int ti1, int tj1) {      // tile (ti, tj) and, if ti1 >= 0, tile (ti1, tj1)
-          auto ext = [&](int a, int b) { return (start[a + 1] - start[a]) | ((start[b + 1] - start[b]) << 8) | ((a == b ? 1 : 0) << 16); };
-          RPair it; it.cone = ci; it.i0 = 16 * start[ti]; it.j0 = 16 * start[tj]; it.ld = bc.ld; it.d = bc.d; it.woff = bc.woff; it.pad = 0;
-          it.ext0 = ext(ti, tj);
-          it.i1 = ti1 >= 0 ? 16 * start[ti1] : it.i0; it.j1 = ti1 >= 0 ? 16 * start[tj1] : it.j0;
-          it.ext1 = ti1 >= 0 ? ext(ti1, tj1) : 0;
-          xp[x].push_back(it);
-        };
-        if (q->df_pair == 2) { for (int tj = 0; tj < nt; ++tj) for (int ti = 0; ti <= tj; ++ti) item(ti, tj, -1, -1); }
-        else {
-          int left = -1;                                         // a block row whose last tile waits for a partner in the last column
-          for (int ti = 0; ti < nt; ++ti)
-            for (int tj = ti; tj < nt; tj += 2) {
-              if (tj + 1 < nt) item(ti, tj, ti, tj + 1);
-              else if (q->df_pair != 3) item(ti, tj, -1, -1);
-              else if (left < 0) left = ti;
-              else { item(left, tj, ti, tj); left = -1; }
-            }
-          if (left >= 0) item(left, nt - 1, -1, -1);
-        }
-      }
-      // Launch order inside an XCD's list = decreasing modelled cost of a tile (k-panels x slots of its fullest wave, in units of a tenth
-      // of a slot, + a fixed part for prologue and epilogue): the hardware hands the next workgroup to the first free slot, i.e. it runs
-      // longest-processing-time-first list scheduling if the list is sorted -- with ~1.5 tiles per slot the order of the cones (by leading
-      // dimension only) left expensive tiles for the tail.  35.8 -> 32.0 us per product on BASELINE config 5 (COSMO_HIP_POLAR_BATCH_SORT=0
-      // keeps the cone order; three alternating pairs of runs, profiles/r03_cfg5_ragged.txt).  A cone's tiles of one shape stay adjacent
-      // (stable sort), so they still meet in the XCD's L2.
-      int sort_tiles = 1;
-      if (const char* e = getenv("COSMO_HIP_POLAR_BATCH_SORT")) sort_tiles = atoi(e) ? 1 : 0;
-      if (sort_tiles) {
-        auto cost = [](const RTile& t) {
-          const int ei = t.ext & 255, ej = (t.ext >> 8) & 255, dg = (t.ext >> 16) & 1;
-          const int nblk = dg ? ei * (ei + 1) / 2 : ei * ej, slots = (nblk + 3) / 4;
-          return (long long)((t.d + 15) / 16) * (10 * slots + 2) + 125;
-        };
-        for (int x = 0; x < 8; ++x) std::stable_sort(xl[x].begin(), xl[x].end(), [&](const RTile& a, const RTile& b) { return cost(a) > cost(b); });
-        auto pcost = [&](const RPair& it) {            // an item costs what its busier half costs
-          RTile t; t.d = it.d; t.ext = it.ext0;
-          const long long c0 = cost(t);
-          if (!it.ext1) return c0;
-          t.ext = it.ext1;
-          return std::max(c0, cost(t));
-        };
-        for (int x = 0; x < 8; ++x) std::stable_sort(xp[x].begin(), xp[x].end(), [&](const RPair& a, const RPair& b) { return pcost(a) > pcost(b); });
-      }
-      size_t maxlen = 0;
-      for (int x = 0; x < 8; ++x) maxlen = std::max(maxlen, xl[x].size());
-      std::vector<RTile> rl(8 * std::max<size_t>(maxlen, 1), RTile{-1, 0, 0, 0, 0, 0, 0});
-      for (int x = 0; x < 8; ++x) for (size_t sl = 0; sl < xl[x].size(); ++sl) rl[8 * sl + x] = xl[x][sl];
-      q->nrtiles = (int)rl.size();
-      { // the same per-XCD lists, contiguous, for the persistent dependency-driven launch of the main schedule
-        std::vector<int> cnt(q->bcones.size(), 0);      // items per cone: what a cone's completion counter gains per product
-        q->df_ntiles = 0;
-        for (int x = 0; x < 8; ++x) q->df_ntiles += (int)xl[x].size();
-        if (q->df_pair) {
-          std::vector<RPair> dl;
-          for (int x = 0; x < 8; ++x) { q->df_xoff[x] = (int)dl.size(); for (const RPair& t : xp[x]) { dl.push_back(t); cnt[(size_t)t.cone] += 1; } }
-          q->df_xoff[8] = (int)dl.size();
-          if (dl.empty()) dl.push_back(RPair{-1, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0});
-          HIPCHK(h, hipMalloc((void**)&q->d_df_tiles, sizeof(RPair) * dl.size()));
-          HIPCHK(h, hipMemcpy(q->d_df_tiles, dl.data(), sizeof(RPair) * dl.size(), hipMemcpyHostToDevice));
-        } else {
-          std::vector<RTile> dl;
-          for (int x = 0; x < 8; ++x) { q->df_xoff[x] = (int)dl.size(); for (const RTile& t : xl[x]) { dl.push_back(t); cnt[(size_t)t.cone] += 1; } }
-          q->df_xoff[8] = (int)dl.size();
-          if (dl.empty()) dl.push_back(RTile{-1, 0, 0, 0, 0, 0, 0});
-          HIPCHK(h, hipMalloc((void**)&q->d_df_tiles, sizeof(RTile) * dl.size()));
-          HIPCHK(h, hipMemcpy(q->d_df_tiles, dl.data(), sizeof(RTile) * dl.size(), hipMemcpyHostToDevice));
-        }
-        HIPCHK(h, hipMalloc((void**)&q->d_df_cone_nt, sizeof(int) * std::max<size_t>(cnt.size(), 1)));
-        HIPCHK(h, hipMemcpy(q->d_df_cone_nt, cnt.data(), sizeof(int) * cnt.size(), hipMemcpyHostToDevice));
-        HIPCHK(h, hipMalloc((void**)&q->d_df_sync, sizeof(unsigned) * (DF_SYNC_DONE + cnt.size())));
-        hipDeviceProp_t prop;
-        HIPCHK(h, hipGetDeviceProperties(&prop, h->device));
-        // The grid is four workgroups per CU in both forms (the launch shape polar_dataflow_stats reports).  The 256-thread form has them all resident; of the
-        // 512-thread form two per CU are (16 waves per CU either way): they drain the queues, and the other half starts when the first leave, draws a ticket
-        // past the end of its queue and returns -- an item waits only for earlier items of its queue, so nothing depends on who is resident.
-        const int slots = std::max(1, prop.multiProcessorCount) * (q->df_pair ? 2 : 4);      // workgroups resident at a time
-        q->df_grid = std::max(1, prop.multiProcessorCount) * 4;
-        // DEFAULT: on where every XCD's list holds at least as many tiles as the XCD has workgroup slots (BASELINE config 5: 188 tiles, 128 slots:
-        // 4.035 -> 3.897 ms per ADMM iteration, same bits).  A small batch (40 cliques: ~17 tiles per XCD) has nothing to overlap -- its products are
-        // already shorter than a launch ramp -- and pays a dependency wait per tile: 1.48 -> 1.79 ms, so it keeps the launch-per-product form.
-        { int nmin = INT32_MAX; for (int x = 0; x < 8; ++x) nmin = std::min(nmin, q->df_xoff[x + 1] - q->df_xoff[x]); q->dataflow = (nmin >= slots / 8) ? 1 : 0; }
-        if (const char* e = getenv("COSMO_HIP_POLAR_DATAFLOW")) q->dataflow = atoi(e) ? 1 : 0;
-        if (const char* e = getenv("COSMO_HIP_POLAR_DATAFLOW_GRID")) { const int v = atoi(e); if (v >= 8 && v <= 8192) q->df_grid = v; }
-        (void)hipFuncSetAttribute((const void*)k_polar_dataflow<4>, hipFuncAttributeMaxDynamicSharedMemorySize, GemmCfg<64>::SMEM);
-        (void)hipFuncSetAttribute((const void*)k_polar_dataflow_pair<4>, hipFuncAttributeMaxDynamicSharedMemorySize, DF_PAIR_SMEM); }
-      HIPCHK(h, hipMalloc((void**)&q->d_rtiles, sizeof(RTile) * rl.size()));
-      HIPCHK(h, hipMemcpy(q->d_rtiles, rl.data(), sizeof(RTile) * rl.size(), hipMemcpyHostToDevice));
-      q->h_rtiles = malloc(sizeof(RTile) * rl.size());
+      q->nrtiles = (int)bp.rtiles.size();
+      q->df_ntiles = bp.df_ntiles;
+      for (int x = 0; x <= kPolarXcds; ++x) q->df_xoff[x] = bp.xoff[x];
+      // the per-XCD lists, contiguous, for the persistent dependency-driven launch of the main schedule
+      if (q->df_pair) CHK(polar_upload(h, &q->d_df_tiles, bp.pairs.data(), sizeof(RPair) * bp.pairs.size()));
+      else CHK(polar_upload(h, &q->d_df_tiles, bp.items.data(), sizeof(RTile) * bp.items.size()));
+      CHK(polar_upload(h, &q->d_df_cone_nt, bp.cone_nt.data(), sizeof(int) * nb));
+      HIPCHK(h, hipMalloc((void**)&q->d_df_sync, sizeof(unsigned) * (DF_SYNC_DONE + nb)));
+      hipDeviceProp_t prop;
+      HIPCHK(h, hipGetDeviceProperties(&prop, h->device));
+      // The grid is four workgroups per CU in both forms (the launch shape polar_dataflow_stats reports).  The 256-thread form has them all resident; of the
+      // 512-thread form two per CU are (16 waves per CU either way): they drain the queues, and the other half starts when the first leave, draws a ticket
+      // past the end of its queue and returns -- an item waits only for earlier items of its queue, so nothing depends on who is resident.
+      const int slots = std::max(1, prop.multiProcessorCount) * (q->df_pair ? 2 : 4);      // workgroups resident at a time
+      q->df_grid = k.dataflow_grid >= 0 ? k.dataflow_grid : std::max(1, prop.multiProcessorCount) * 4;
+      // DEFAULT: on where every XCD's list holds at least as many tiles as the XCD has workgroup slots (BASELINE config 5: 188 tiles, 128 slots:
+      // 4.035 -> 3.897 ms per ADMM iteration, same bits).  A small batch (40 cliques: ~17 tiles per XCD) has nothing to overlap -- its products are
+      // already shorter than a launch ramp -- and pays a dependency wait per tile: 1.48 -> 1.79 ms, so it keeps the launch-per-product form.
+      int nmin = INT32_MAX;
+      for (int x = 0; x < kPolarXcds; ++x) nmin = std::min(nmin, q->df_xoff[x + 1] - q->df_xoff[x]);
+      q->dataflow = k.dataflow >= 0 ? k.dataflow : (nmin >= slots / kPolarXcds ? 1 : 0);
+      // the XCD-interleaved list of the launch-per-product form, its host copy and the staging of the compact repair list
+      const size_t rbytes = sizeof(RTile) * bp.rtiles.size();
+      CHK(polar_upload(h, &q->d_rtiles, bp.rtiles.data(), rbytes));
+      q->h_rtiles = malloc(rbytes);
       if (!q->h_rtiles) return cosmo_fail(h, COSMO_HIP_ERR_HIP, "out of host memory");
-      memcpy(q->h_rtiles, rl.data(), sizeof(RTile) * rl.size());
-      HIPCHK(h, hipMalloc((void**)&q->d_rtiles_rep, sizeof(RTile) * rl.size()));
-      HIPCHK(h, hipHostMalloc((void**)&q->rep_host, sizeof(RTile) * rl.size()));
-      (void)hipFuncSetAttribute((const void*)k_symm_gemm_batch_r<0, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, GemmCfg<64>::SMEM);
-      (void)hipFuncSetAttribute((const void*)k_symm_gemm_batch_r<1, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, GemmCfg<64>::SMEM);
-      (void)hipFuncSetAttribute((const void*)k_symm_gemm_batch_r<0, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, GemmCfg<64>::SMEM);
-      (void)hipFuncSetAttribute((const void*)k_symm_gemm_batch_r<1, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, GemmCfg<64>::SMEM);
-    } else {
-      for (const BatchCone& bc : q->bcones) { const long long nt = bc.ld / bc.ts; q->batch_flops_performed += 2.0 * (double)(nt * (nt + 1) / 2) * bc.ts * bc.ts * (((bc.d + 31) / 32) * 32); }
+      memcpy(q->h_rtiles, bp.rtiles.data(), rbytes);
+      HIPCHK(h, hipMalloc((void**)&q->d_rtiles_rep, rbytes));
+      HIPCHK(h, hipHostMalloc((void**)&q->rep_host, rbytes));
     }
-    if (tiles.empty()) tiles.push_back(int4{-1, 0, 0, 0});
-    HIPCHK(h, hipMalloc((void**)&q->BW, sizeof(real) * (size_t)woff));
+    HIPCHK(h, hipMalloc((void**)&q->BW, sizeof(real) * (size_t)bp.work));
     // the ragged product kernel writes a cone's d16 x d16 corner only: the padding up to ld must be zero from the start (populate / scale keep
     // it zero in X and U; Y and T are never written there), because the verification sums run over whole ld x ld buffers
-    HIPCHK(h, hipMemset(q->BW, 0, sizeof(real) * (size_t)woff));
-    HIPCHK(h, hipMalloc((void**)&q->d_bcones, sizeof(BatchCone) * q->bcones.size()));
-    HIPCHK(h, hipMalloc((void**)&q->d_btiles, sizeof(int4) * tiles.size()));
-    HIPCHK(h, hipMalloc((void**)&q->bparts, sizeof(real) * 3 * BPX * q->bcones.size()));   // norm, trace and verification partials
-    HIPCHK(h, hipMalloc((void**)&q->bnrm, sizeof(real) * q->bcones.size()));
-    HIPCHK(h, hipMalloc((void**)&q->bgate, sizeof(int) * q->bcones.size()));
-    HIPCHK(h, hipMemset(q->bgate, 0, sizeof(int) * q->bcones.size()));
-    { const size_t nb = q->bcones.size();
-      { int pat = 3; if (const char* e = getenv("COSMO_HIP_POLAR_PATIENCE")) pat = std::max(1, atoi(e));      // verified projections before a cone probes one step down
-        q->bk.assign(nb, q->k_lift); q->bstreak.assign(nb, 0); q->bm.assign(nb, pat); }
-      HIPCHK(h, hipMalloc((void**)&q->d_lgate, sizeof(int) * nb * POLAR_LIFT_CAP));
-      HIPCHK(h, hipMalloc((void**)&q->d_ubuf, sizeof(int) * nb));
-      HIPCHK(h, hipHostMalloc((void**)&q->bgate_host, sizeof(int) * nb, hipHostMallocDefault));
-      q->lgate_kmax = -1; }
-    HIPCHK(h, hipMemcpy(q->d_bcones, q->bcones.data(), sizeof(BatchCone) * q->bcones.size(), hipMemcpyHostToDevice));
-    HIPCHK(h, hipMemcpy(q->d_btiles, tiles.data(), sizeof(int4) * tiles.size(), hipMemcpyHostToDevice));
-    (void)hipFuncSetAttribute((const void*)k_symm_gemm_batch<0, 3, 64>, hipFuncAttributeMaxDynamicSharedMemorySize, GemmCfg<64>::SMEM);
-    (void)hipFuncSetAttribute((const void*)k_symm_gemm_batch<1, 3, 64>, hipFuncAttributeMaxDynamicSharedMemorySize, GemmCfg<64>::SMEM);
-    (void)hipFuncSetAttribute((const void*)k_symm_gemm_batch<0, 4, 64>, hipFuncAttributeMaxDynamicSharedMemorySize, GemmCfg<64>::SMEM);
-    (void)hipFuncSetAttribute((const void*)k_symm_gemm_batch<1, 4, 64>, hipFuncAttributeMaxDynamicSharedMemorySize, GemmCfg<64>::SMEM);
-    (void)hipFuncSetAttribute((const void*)k_symm_gemm_batch<0, 2, 96>, hipFuncAttributeMaxDynamicSharedMemorySize, GemmCfg<96>::SMEM);
-    (void)hipFuncSetAttribute((const void*)k_symm_gemm_batch<1, 2, 96>, hipFuncAttributeMaxDynamicSharedMemorySize, GemmCfg<96>::SMEM);
+    HIPCHK(h, hipMemset(q->BW, 0, sizeof(real) * (size_t)bp.work));
+    CHK(polar_upload(h, &q->d_bcones, q->bcones.data(), sizeof(BatchCone) * nb));
+    CHK(polar_upload(h, &q->d_btiles, bp.qtiles.data(), sizeof(QTile) * bp.qtiles.size()));
+    HIPCHK(h, hipMalloc((void**)&q->bparts, sizeof(real) * 3 * BPX * nb));   // norm, trace and verification partials
+    HIPCHK(h, hipMalloc((void**)&q->bnrm, sizeof(real) * nb));
+    HIPCHK(h, hipMalloc((void**)&q->bgate, sizeof(int) * nb));
+    HIPCHK(h, hipMemset(q->bgate, 0, sizeof(int) * nb));
+    q->bdepth.assign(nb, LiftDepth{q->k_lift, 0, k.patience});
+    HIPCHK(h, hipMalloc((void**)&q->d_lgate, sizeof(int) * nb * POLAR_LIFT_CAP));
+    HIPCHK(h, hipMalloc((void**)&q->d_ubuf, sizeof(int) * nb));
+    HIPCHK(h, hipHostMalloc((void**)&q->bgate_host, sizeof(int) * nb, hipHostMallocDefault));
+    q->lgate_kmax = -1;
     // Ragged kernel: FOUR workgroups per CU by default (<= 128 VGPRs: one staging set, panels requested one step ahead).  Its main loops are
     // at the pace of the matrix pipe whenever three of them share a SIMD; what the fourth wave fills is the pipe time of the others'
     // prologues and epilogues: 36.0 vs 39.0 us per product on BASELINE config 5 (four alternating pairs of runs, 166.2 vs 162.9 it/s;
     // profiles/r03_cfg5_ragged.txt).  The quadrant kernel stays at three (there four were slower, see k_symm_gemm_batch).
-    q->batch_occ = q->batch_ragged ? 4 : 3;
-    if (const char* e = getenv("COSMO_HIP_POLAR_BATCH_OCC")) { const int v = atoi(e); if (v == 3 || v == 4) q->batch_occ = v; }
+    q->batch_occ = k.occ >= 0 ? k.occ : (q->batch_ragged ? 4 : 3);
   }
+  polar_set_func_attributes(q);
   return COSMO_HIP_OK;
 }
 
@@ -1968,25 +1852,21 @@ bool polar_has_large(const cosmo_hip_handle* h) { const PolarPlan* q = static_ca
 // 74.5 KB of LDS allow two workgroups per CU)
 template <int EPI>
 static void launch_bgemm(PolarPlan* q, hipStream_t st, const Ctl* ctl, int guard, const int* gate, int ia, int ib, int icin, int ic, real alpha, real beta) {
+  // the register-allocation variant of the plan: 3 or 4 waves per SIMD (ragged default: four workgroups per CU, <= 128 VGPRs: one staging set,
+  // operand panels requested ONE step ahead)
+  auto ragged = [&](int ntiles, const void* tiles) {
+    const auto kern = q->batch_occ == 4 ? k_symm_gemm_batch_r<EPI, 4> : k_symm_gemm_batch_r<EPI, 3>;
+    hipLaunchKernelGGL(kern, dim3(ntiles), dim3(256), GemmCfg<64>::SMEM, st, ctl, guard, gate, (const RTile*)tiles, q->d_bcones, q->BW, ia, ib, icin, ic, alpha, beta);
+  };
   if (q->batch_ragged && q->nrep > 0) {          // compact repair launch: the failing cones' tiles only (no gate needed: the list IS the gate)
-    if (q->batch_occ == 4)
-      hipLaunchKernelGGL((k_symm_gemm_batch_r<EPI, 4>), dim3(q->nrep), dim3(256), GemmCfg<64>::SMEM, st, ctl, guard, gate, (const RTile*)q->d_rtiles_rep, q->d_bcones,
-                         q->BW, ia, ib, icin, ic, alpha, beta);
-    else
-      hipLaunchKernelGGL((k_symm_gemm_batch_r<EPI, 3>), dim3(q->nrep), dim3(256), GemmCfg<64>::SMEM, st, ctl, guard, gate, (const RTile*)q->d_rtiles_rep, q->d_bcones,
-                         q->BW, ia, ib, icin, ic, alpha, beta);
+    ragged(q->nrep, q->d_rtiles_rep);
     q->repair_launch_tiles += q->nrep;
     return;
   }
   if (q->batch_ragged && q->nrtiles > 0) {
     // (the two halves of the batch on two HIP streams -- so that one half's launch tail overlaps the other's steady state -- were built and
     //  measured: 187.8-189.6 vs 187.1 it/s on BASELINE config 5, no gain, removed; profiles/r03_cfg5_ragged.txt)
-    if (q->batch_occ == 4)        // default: four workgroups per CU (<= 128 VGPRs: one staging set, operand panels requested ONE step ahead)
-      hipLaunchKernelGGL((k_symm_gemm_batch_r<EPI, 4>), dim3(q->nrtiles), dim3(256), GemmCfg<64>::SMEM, st, ctl, guard, gate, (const RTile*)q->d_rtiles, q->d_bcones,
-                         q->BW, ia, ib, icin, ic, alpha, beta);
-    else
-      hipLaunchKernelGGL((k_symm_gemm_batch_r<EPI, 3>), dim3(q->nrtiles), dim3(256), GemmCfg<64>::SMEM, st, ctl, guard, gate, (const RTile*)q->d_rtiles, q->d_bcones,
-                         q->BW, ia, ib, icin, ic, alpha, beta);
+    ragged(q->nrtiles, q->d_rtiles);
     return;
   }
   if (q->nbtiles96 > 0)
@@ -1995,34 +1875,28 @@ static void launch_bgemm(PolarPlan* q, hipStream_t st, const Ctl* ctl, int guard
   if (q->nbtiles > 0 && q->batch_wave) {
     hipLaunchKernelGGL((k_symm_gemm_batch_w<EPI>), dim3(q->nbtiles), dim3(64), 0, st, ctl, guard, gate, q->d_btiles, q->d_bcones, q->BW, ia, ib, icin, ic, alpha, beta);
   } else if (q->nbtiles > 0) {
-    if (q->batch_occ == 4)
-      hipLaunchKernelGGL((k_symm_gemm_batch<EPI, 4, 64>), dim3(q->nbtiles), dim3(256), GemmCfg<64>::SMEM, st, ctl, guard, gate, q->d_btiles, q->d_bcones, q->BW,
-                         ia, ib, icin, ic, alpha, beta);
-    else
-      hipLaunchKernelGGL((k_symm_gemm_batch<EPI, 3, 64>), dim3(q->nbtiles), dim3(256), GemmCfg<64>::SMEM, st, ctl, guard, gate, q->d_btiles, q->d_bcones, q->BW,
-                         ia, ib, icin, ic, alpha, beta);
+    const auto kern = q->batch_occ == 4 ? k_symm_gemm_batch<EPI, 4, 64> : k_symm_gemm_batch<EPI, 3, 64>;
+    hipLaunchKernelGGL(kern, dim3(q->nbtiles), dim3(256), GemmCfg<64>::SMEM, st, ctl, guard, gate, q->d_btiles, q->d_bcones, q->BW, ia, ib, icin, ic, alpha, beta);
   }
 }
 
 // all mid-size cones of the batch advance together: 3 launches per step for the whole batch; with the per-cone lifting depth (PolarPlan::adapt) a
-// cone joins at lifting step kmax - bk[c] and the product kernels skip its tiles before that
+// cone joins at lifting step kmax - bdepth[c].k and the product kernels skip its tiles before that
 int32_t polar_enqueue_project_batch(cosmo_hip_handle* h, real* s, int guard) {
   PolarPlan* q = static_cast<PolarPlan*>(h->psd_polar);
   PsdPlan* p = h->psd;
   hipStream_t st = h->stream;
   const int n = (int)q->bcones.size();
   real* vparts = q->bparts + (size_t)2 * BPX * n;
-  // adaptive per-cone depth needs the per-cone verification results on the host: not in speculative mode (no synchronisation inside a projection),
-  // not with a schedule forced through COSMO_HIP_POLAR_KLIFT
-  const bool adapt = q->adapt && !q->speculate && !getenv("COSMO_HIP_POLAR_KLIFT") && q->k_lift <= POLAR_LIFT_CAP;
+  const bool adapt = q->adaptive();
   int kmax = q->k_lift;
   if (adapt) {
     kmax = 0;
-    for (int c = 0; c < n; ++c) kmax = std::max(kmax, q->bk[c]);
-    if (q->lgate_kmax != kmax) {                     // (a change of any bk[c] resets lgate_kmax to -1)
+    for (int c = 0; c < n; ++c) kmax = std::max(kmax, q->bdepth[c].k);
+    if (q->lgate_kmax != kmax) {                     // (a change of any depth resets lgate_kmax to -1)
       std::vector<int> lg((size_t)std::max(kmax, 1) * n, 0), ub((size_t)n, 1);
       for (int c = 0; c < n; ++c) {
-        const int t0 = kmax - q->bk[c];
+        const int t0 = kmax - q->bdepth[c].k;
         for (int t = t0; t < kmax; ++t) lg[(size_t)t * n + c] = 1;
         ub[(size_t)c] = (t0 & 1) ? 2 : 1;            // (iu, iy) = (1, 2) at even steps, (2, 1) at odd ones
       }
@@ -2092,7 +1966,7 @@ int32_t polar_enqueue_project_batch(cosmo_hip_handle* h, real* s, int guard) {
   CHK(verify(0, nullptr));
   q->products_last_batch = products;
   { double wsum = 0.0, w3 = 0.0;                             // what the launches cost: products of a cone weighted by its d^3
-    for (int c = 0; c < n; ++c) { const double d3 = (double)q->bcones[c].d * q->bcones[c].d * q->bcones[c].d; w3 += d3; wsum += d3 * (3.0 * ((adapt ? q->bk[c] : kmax) + POLAR_NFIN) + 2.0); }
+    for (int c = 0; c < n; ++c) { const double d3 = (double)q->bcones[c].d * q->bcones[c].d * q->bcones[c].d; w3 += d3; wsum += d3 * (3.0 * ((adapt ? q->bdepth[c].k : kmax) + POLAR_NFIN) + 2.0); }
     q->wprod_last = w3 > 0.0 ? wsum / w3 : 0.0; }
   for (int r = 1; r <= q->max_rounds; ++r) {                 // guarded fallback rounds (even number of steps: iu is preserved)
     if (!q->speculate) {                                     // ask the device whether the last verification failed (and, round 1 of an adaptive run, which cones)
@@ -2106,14 +1980,8 @@ int32_t polar_enqueue_project_batch(cosmo_hip_handle* h, real* s, int guard) {
         q->depth_proj += 1;
         bool changed = false;
         for (int c = 0; c < n; ++c) {
-          if (*q->gate_host && q->bgate_host[c]) {           // failed at depth bk[c]: one step deeper, probe downwards half as often
-            q->depth_fail += 1;
-            if (q->bk[c] < POLAR_LIFT_CAP) { q->bk[c] += 1; changed = true; }
-            q->bstreak[c] = 0;
-            q->bm[c] = std::min(96, 2 * q->bm[c]);
-          } else if (++q->bstreak[c] >= q->bm[c] && q->bk[c] > 0) {
-            q->bk[c] -= 1; q->bstreak[c] = 0; q->depth_down += 1; changed = true;
-          }
+          if (*q->gate_host && q->bgate_host[c]) { q->depth_fail += 1; if (q->bdepth[c].fail(POLAR_LIFT_CAP)) changed = true; }
+          else if (q->bdepth[c].pass(0)) { q->depth_down += 1; changed = true; }
         }
         if (changed) q->lgate_kmax = -1;
       }
@@ -2176,9 +2044,9 @@ int32_t polar_enqueue_project(cosmo_hip_handle* h, real* s, int guard) {
                          q->nrm + ci, q->tol_factor * cn.d * PSD_EPS);
       products += 2;
     };
-    const bool adapt = q->adapt && !q->speculate && !getenv("COSMO_HIP_POLAR_KLIFT") && q->k_lift <= POLAR_LIFT_CAP;
-    if (adapt && q->lk.size() != q->cones.size()) { q->lk.assign(q->cones.size(), q->k_lift); q->lstreak.assign(q->cones.size(), 0); q->lm.assign(q->cones.size(), 3); }
-    int k_main = adapt ? q->lk[ci] : q->k_lift;
+    const bool adapt = q->adaptive();
+    if (adapt && q->ldepth.size() != q->cones.size()) q->ldepth.assign(q->cones.size(), LiftDepth{q->k_lift, 0, 3});
+    int k_main = adapt ? q->ldepth[ci].k : q->k_lift;
     if (q->rescale && k_main > 0) {
       // first lifting step with the spectral rescaling between its first and second product; from d = 1024 on the gain (>= 4.2)
       // exceeds the slope of a lifting step, so the main schedule is one step shorter
@@ -2203,8 +2071,8 @@ int32_t polar_enqueue_project(cosmo_hip_handle* h, real* s, int guard) {
         if (adapt && r == 1 && q->gate_host[4] != q->seen_proj_large) {        // depth control of this cone (see PolarPlan::adapt)
           q->seen_proj_large = q->gate_host[4];
           q->depth_proj += 1;
-          if (*q->gate_host) { q->depth_fail += 1; q->lk[ci] = std::min(POLAR_LIFT_CAP, q->lk[ci] + 1); q->lstreak[ci] = 0; q->lm[ci] = std::min(96, 2 * q->lm[ci]); }
-          else if (++q->lstreak[ci] >= q->lm[ci] && q->lk[ci] > 2) { q->lk[ci] -= 1; q->lstreak[ci] = 0; q->depth_down += 1; }
+          if (*q->gate_host) { q->depth_fail += 1; q->ldepth[ci].fail(POLAR_LIFT_CAP); }
+          else if (q->ldepth[ci].pass(2)) q->depth_down += 1;                    // a large cone keeps at least two lifting steps
         }
         if (!*q->gate_host) break;
       }
@@ -2227,7 +2095,7 @@ int32_t polar_enqueue_project(cosmo_hip_handle* h, real* s, int guard) {
 // runs (every rank must keep the schedule of the single-rank run so that the exchanged slices stay bit-identical to it).
 int32_t polar_adapt(cosmo_hip_handle* h) {
   PolarPlan* q = static_cast<PolarPlan*>(h->psd_polar);
-  if (!q || !q->dev || h->comm || getenv("COSMO_HIP_POLAR_KLIFT")) return COSMO_HIP_OK;
+  if (!q || !q->dev || h->comm || q->klift_forced) return COSMO_HIP_OK;
   if (q->adapt && !q->speculate) return COSMO_HIP_OK;          // the per-cone depth control (PolarPlan::adapt) has taken over
   PolarDev now;
   HIPCHK(h, hipMemcpyAsync(&now, q->dev, sizeof now, hipMemcpyDeviceToHost, h->stream));
@@ -2290,12 +2158,12 @@ extern "C" int32_t cosmo_hip_polar_depth_stats(cosmo_hip_handle* h, int64_t out[
   for (int i = 0; i < 8; ++i) out[i] = 0;
   PolarPlan* q = static_cast<PolarPlan*>(h->psd_polar);
   if (!q) return COSMO_HIP_OK;
-  const bool adapt = q->adapt && !q->speculate && !getenv("COSMO_HIP_POLAR_KLIFT") && q->k_lift <= POLAR_LIFT_CAP;
+  const bool adapt = q->adaptive();
   out[0] = adapt ? 1 : 0;
-  const std::vector<int>& ks = !q->bk.empty() ? q->bk : q->lk;
+  const std::vector<LiftDepth>& ks = !q->bdepth.empty() ? q->bdepth : q->ldepth;
   if (adapt && !ks.empty()) {
-    long long sum = 0; int mn = ks[0], mx = ks[0];
-    for (int v : ks) { sum += v; mn = std::min(mn, v); mx = std::max(mx, v); }
+    long long sum = 0; int mn = ks[0].k, mx = ks[0].k;
+    for (const LiftDepth& v : ks) { sum += v.k; mn = std::min(mn, v.k); mx = std::max(mx, v.k); }
     out[1] = mn; out[2] = mx; out[3] = (1000 * sum) / (long long)ks.size();
   } else { out[1] = out[2] = q->k_lift; out[3] = 1000LL * q->k_lift; }
   out[4] = (int64_t)llround(1000.0 * q->wprod_last);
