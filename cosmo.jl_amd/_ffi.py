@@ -163,6 +163,11 @@ SIGNATURES = {
     "cosmo_hip_batch_update_qb": (C.c_int32, [C.c_void_p, C.c_int64, _PI64, _PR, _PR]),
     "cosmo_hip_batch_warm_restart": (C.c_int32, [C.c_void_p]),
     "cosmo_hip_batch_get_qb": (C.c_int32, [C.c_void_p, C.c_int64, _PR, _PR]),
+    "cosmo_hip_batch_stage_matrices": (C.c_int32, [C.c_void_p, C.c_int64, _PR, _PR, C.c_int32]),
+    "cosmo_hip_batch_update_matrices": (C.c_int32, [C.c_void_p, C.c_int64, _PI64, _PR, _PR, C.c_int32]),
+    "cosmo_hip_batch_update_matrices_info": (C.c_int32, [C.c_void_p, _PI64]),
+    "cosmo_hip_batch_get_matrix_values": (C.c_int32, [C.c_void_p, C.c_int64, C.c_int32, _PR]),
+    "cosmo_hip_batch_get_image": (C.c_int32, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, _PI64]),
     "cosmo_hip_batch_scale_ruiz": (C.c_int32, [C.c_void_p, C.c_int64, C.c_double, C.c_double]),
     "cosmo_hip_batch_get_scaling": (C.c_int32, [C.c_void_p, C.c_int64, _PR, _PR, _PD]),
     "cosmo_hip_batch_get_scaled_problem": (C.c_int32, [C.c_void_p, C.c_int64, _PR, _PR, _PR, _PR, _PR, _PR]),
@@ -188,6 +193,7 @@ SIGNATURES = {
     "cosmo_hip_batch_group_get_counters": (C.c_int32, [C.c_void_p, _PI64]),
     "cosmo_hip_batch_group_get_accel_stats": (C.c_int32, [C.c_void_p, _PI64]),
     "cosmo_hip_batch_group_stage_qb": (C.c_int32, [C.c_void_p, C.c_int64, _PR, _PR]),
+    "cosmo_hip_batch_group_stage_matrices": (C.c_int32, [C.c_void_p, C.c_int64, _PR, _PR, C.c_int32]),
     "cosmo_hip_batch_group_apply_updates": (C.c_int32, [C.c_void_p]),
     "cosmo_hip_batch_group_warm_restart": (C.c_int32, [C.c_void_p]),
     "cosmo_hip_batch_group_get_qb": (C.c_int32, [C.c_void_p, C.c_int64, _PR, _PR]),
@@ -709,6 +715,7 @@ class Batch:
         q = self._f(q, self.n, "q"); b = self._f(b, self.m, "b")
         self._chk(self.lib.cosmo_hip_batch_set_problem(self._b, int(k), pc.ctypes.data_as(_PI64), pr.ctypes.data_as(_PI64), _dp(pv),
                                                        ac.ctypes.data_as(_PI64), ar.ctypes.data_as(_PI64), _dp(av), _dp(q), _dp(b)))
+        self.__dict__.setdefault("nnz", {})[int(k)] = (int(pv.size), int(av.size))
 
     def set_cones(self, types, dims, box_l=None, box_u=None, cone_param=None):
         t = np.ascontiguousarray(types, dtype=np.int32); d = np.ascontiguousarray(dims, dtype=np.int64)
@@ -759,6 +766,44 @@ class Batch:
     def stage_qb(self, k, q=None, b=None):
         """Stage the RAW (unscaled) q and / or b of member k for the next apply_updates (host only)."""
         self._chk(self.lib.cosmo_hip_batch_stage_qb(self._b, int(k), _dp(self._f(q, self.n, "q")), _dp(self._f(b, self.m, "b"))))
+
+    def stage_matrices(self, k, P_vals=None, A_vals=None, apply_scaling=False):
+        """Stage new VALUES of P and / or A of member k (the order of set_problem's CSC arrays, same pattern) for the next apply_updates (host only).
+        apply_scaling: the device applies the batch's D, E, c; else the values are taken as given."""
+        nP, nA = getattr(self, "nnz", {}).get(int(k), (None, None))           # (an index the library refuses: its error, not a KeyError)
+        self._chk(self.lib.cosmo_hip_batch_stage_matrices(self._b, int(k), _dp(self._f(P_vals, nP, "P values")), _dp(self._f(A_vals, nA, "A values")),
+                                                          1 if apply_scaling else 0))
+
+    def update_matrices(self, members, P_vals=None, A_vals=None, apply_scaling=False):
+        """stage_matrices of len(members) members (P_vals / A_vals: the members' value arrays one after the other, or None), then apply_updates."""
+        mem = np.ascontiguousarray(members, dtype=np.int64)
+        nP = sum(self.nnz[int(k)][0] for k in mem); nA = sum(self.nnz[int(k)][1] for k in mem)
+        self._chk(self.lib.cosmo_hip_batch_update_matrices(self._b, mem.size, mem.ctypes.data_as(_PI64), _dp(self._f(P_vals, nP, "P values")),
+                                                           _dp(self._f(A_vals, nA, "A values")), 1 if apply_scaling else 0))
+
+    def update_matrices_info(self):
+        """dict(updates, arrays_per_update, host_rebuilds, last_bytes, map_bytes, factorizations) of the matrix updates of this batch."""
+        out = np.zeros(8, dtype=np.int64)
+        self._chk(self.lib.cosmo_hip_batch_update_matrices_info(self._b, out.ctypes.data_as(_PI64)))
+        keys = ("updates", "arrays_per_update", "host_rebuilds", "last_bytes", "map_bytes", "factorizations")
+        return dict(zip(keys, (int(v) for v in out[:6])))
+
+    def get_matrix_values(self, k, which):
+        """The device copy of member k's values: which = 0 / 'A' the CSR of A, 1 / 'AT' the CSR of A' (CSC order of A), 2 / 'PT' the rows of [P | A']."""
+        w = {"A": 0, "AT": 1, "PT": 2}.get(which, which)
+        nP, nA = self.nnz[int(k)]
+        out = np.empty(nP + nA if w == 2 else nA, dtype=self.dtype)
+        self._chk(self.lib.cosmo_hip_batch_get_matrix_values(self._b, int(k), int(w), _dp(out)))
+        return out
+
+    def get_image(self, k):
+        """The raw bytes of member k's LDS image followed by its row of the register-resident diagonal of P (empty for a batch that has neither)."""
+        nb = C.c_int64(0)
+        self._chk(self.lib.cosmo_hip_batch_get_image(self._b, int(k), None, 0, C.byref(nb)))
+        out = np.zeros(int(nb.value), dtype=np.uint8)
+        if out.size:
+            self._chk(self.lib.cosmo_hip_batch_get_image(self._b, int(k), out.ctypes.data_as(C.c_void_p), out.size, C.byref(nb)))
+        return out
 
     def apply_updates(self):
         """Every staged vector in one copy and one launch: scaled on the device, rows of Nonnegatives cones re-classified."""
@@ -915,6 +960,7 @@ class BatchGroup:
         self._chk(self.lib.cosmo_hip_batch_group_set_problem(self._g, int(k), int(n), int(m), pc.ctypes.data_as(_PI64), pr.ctypes.data_as(_PI64), _dp(pv),
                                                              ac.ctypes.data_as(_PI64), ar.ctypes.data_as(_PI64), _dp(av), _dp(q), _dp(b)))
         self.dims[int(k)] = (int(n), int(m))
+        self.__dict__.setdefault("nnz", {})[int(k)] = (int(pv.size), int(av.size))
 
     def set_cones(self, k, types, dims, box_l=None, box_u=None, cone_param=None):
         t = np.ascontiguousarray(types, dtype=np.int32); d = np.ascontiguousarray(dims, dtype=np.int64)
@@ -961,6 +1007,11 @@ class BatchGroup:
     def stage_qb(self, k, q=None, b=None):
         n, m = self.dims[int(k)]
         self._chk(self.lib.cosmo_hip_batch_group_stage_qb(self._g, int(k), _dp(self._f(q, n, "q")), _dp(self._f(b, m, "b"))))
+
+    def stage_matrices(self, k, P_vals=None, A_vals=None, apply_scaling=False):
+        nP, nA = self.nnz[int(k)]
+        self._chk(self.lib.cosmo_hip_batch_group_stage_matrices(self._g, int(k), _dp(self._f(P_vals, nP, "P values")), _dp(self._f(A_vals, nA, "A values")),
+                                                                1 if apply_scaling else 0))
 
     def apply_updates(self):
         self._chk(self.lib.cosmo_hip_batch_group_apply_updates(self._g))

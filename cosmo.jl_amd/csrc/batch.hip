@@ -29,6 +29,7 @@
 #include "cone3.h"
 #include "batch_ldl.h"
 #include "batch_ruiz.h"
+#include "value_maps.h"
 
 struct BCtl {                 // per problem, device resident
   int status; int n_rho_updates;
@@ -2234,6 +2235,47 @@ __global__ __launch_bounds__(256) void k_batch_update_qb(int n, int m, const int
   }
 }
 
+// New values for the stored entries of P and A of the staged members (cosmo_hip_batch_stage_matrices), one workgroup each.  val + off holds the member's
+// raw values in the caller's CSC order, [P_nzval (nnzP) | A_nzval (nnzA)].  Pass 1 (flag bit 2) scales them ONCE, in place, walking the rows of the
+// member's [P | A'] -- which holds every stored entry of P and of A exactly once -- with the expressions of update.hip / model._scale_csc:
+// P_ij <- (p * (D_i * D_j)) * c, A_ij <- a * (E_i * D_j).  Pass 2 is a pure gather dst[p] = val[src[p]] into every value array of the member that the
+// descriptors name (BUPD_ND per member: A, A', [P | A'], the image's Aval and Pval, pdiag), so all copies of an entry hold the same bits.  src < 0
+// (padding of the sliced image, a row of P without its diagonal) and entries of a part that was not staged (flag bit 0: P, bit 1: A) are left alone.
+struct BUpdHdr { int32_t mem, flag, nnzP, nnzA; long long off; };
+struct BUpdDesc { real* dst; const int32_t* map; int count; int base; };        // map == null: src = base + p
+#define BUPD_ND 6
+__global__ __launch_bounds__(256) void k_batch_update_matrices(BatchDev D, const BUpdHdr* __restrict__ hdr, real* __restrict__ val,
+                                                               const BUpdDesc* __restrict__ desc, const real* __restrict__ Dsc,
+                                                               const real* __restrict__ Esc, const real* __restrict__ csc) {
+  const BUpdHdr h = hdr[blockIdx.x];
+  const long long k = h.mem;
+  const int n = D.n, m = D.m, tid = threadIdx.x, bs = blockDim.x;
+  real* v = val + h.off;
+  const BUpdDesc* de = desc + k * BUPD_ND;
+  if (h.flag & 4) {
+    const int* rp = D.PT.rowptr + k * (n + 1);
+    const int* sp = D.PT.split + k * n;
+    const int* col = D.PT.col + D.PT.nz_off[k];
+    const int32_t* pm = de[2].map;
+    const real *Dk = Dsc + k * n, *Ek = Esc + k * m;
+    const real c = csc[k];
+    for (int j = tid; j < n; j += bs) {
+      const real dj = Dk[j];
+      const int p0 = rp[j], ps = sp[j], p1 = rp[j + 1];
+      if (h.flag & 1) for (int p = p0; p < ps; ++p) { const int s = pm[p]; v[s] = (v[s] * (dj * Dk[col[p]])) * c; }
+      if (h.flag & 2) for (int p = ps; p < p1; ++p) { const int s = pm[p]; v[s] = v[s] * (Ek[col[p] - n] * dj); }
+    }
+  }
+  __syncthreads();
+  for (int d = 0; d < BUPD_ND; ++d) {
+    const BUpdDesc e = de[d];
+    for (int p = tid; p < e.count; p += bs) {
+      const int s = e.map ? e.map[p] : e.base + p;
+      if (s >= 0 && (h.flag & (s < h.nnzP ? 1 : 2))) e.dst[p] = v[s];
+    }
+  }
+}
+
 // The next optimize! warm-starts from the batch's own final iterates: reverse_scaling! (src/scaling.jl:170-179) followed by scale_variables!
 // (src/scaling.jl:118-123) as the host does them between two solves, then w = [x; mu ./ rho + s] (solver.jl:128-129) as k_batch_set_w.
 __global__ __launch_bounds__(COSMO_BS) void k_batch_warm_restart(BatchDev D, const real* __restrict__ Dsc, const real* __restrict__ Esc,
@@ -2300,6 +2342,15 @@ struct cosmo_hip_batch {
   // carry a caller's scaling (set_scaling*), whether the pass ran and what it reports (cosmo_hip_batch_ruiz_info)
   std::vector<char> p_sym, caller_scaled;
   bool ruiz_done = false; int64_t ruiz_info[4] = {0, 0, 0, 0};
+  // new matrix values on a finalised batch (cosmo_hip_batch_stage_matrices / apply_updates: k_batch_update_matrices).  Per member and destination
+  // slot the index of its source in the caller's [P_nzval | A_nzval] (CSC order; entries of A carry nnzP on top): um_A for the CSR of A, um_PT for
+  // [P | A'] (set_problem, value_maps.h; A' is the caller's order itself), um_imgA / um_imgP for the member's LDS image and um_pd for its row of pdiag
+  // (build_lds_images carries them next to the values; -1: a padding slot / no entry).  Host only until the first staged update (bupd_init).
+  std::vector<std::vector<int32_t>> um_A, um_PT, um_imgA, um_imgA2, um_imgP, um_pd;
+  std::vector<long long> um_nnzP, um_nnzA, um_offA, um_offPT, um_offV;     // counts; first value of member k in D.A / D.AT, in D.PT, in the staging
+  const int32_t* d_umap = nullptr; const BUpdDesc* d_udesc = nullptr; unsigned char* d_mstage = nullptr;
+  std::vector<int32_t> mstg_slot, mstg_mem, mstg_flag; std::vector<std::vector<real>> mstg_val;
+  long long upd_count = 0, upd_last_bytes = 0, upd_map_bytes = 0, upd_factorisations = 0;
 };
 
 static int32_t bfail(cosmo_hip_batch* b, int32_t code, const char* fmt, ...) {
@@ -2340,6 +2391,8 @@ extern "C" int32_t cosmo_hip_batch_create(cosmo_hip_batch** out, int32_t device_
   b->hA.resize(nprob); b->hAT.resize(nprob); b->hPT.resize(nprob);
   b->hq.assign((size_t)nprob * n, 0.0); b->hb.assign((size_t)nprob * m, 0.0);
   b->have.assign(nprob, 0); b->p_sym.assign(nprob, 0); b->caller_scaled.assign(nprob, 0);
+  b->um_A.resize(nprob); b->um_PT.resize(nprob); b->um_imgA.resize(nprob); b->um_imgA2.resize(nprob); b->um_imgP.resize(nprob); b->um_pd.resize(nprob);
+  b->um_nnzP.assign(nprob, 0); b->um_nnzA.assign(nprob, 0);
   b->hDinv.assign((size_t)nprob * n, 1.0); b->hEinv.assign((size_t)nprob * m, 1.0); b->hcinv.assign(nprob, 1.0);
   b->hD.assign((size_t)nprob * n, 1.0); b->hE.assign((size_t)nprob * m, 1.0); b->hc.assign(nprob, 1.0);
   cosmo_hip_default_params(&b->prm);
@@ -2404,6 +2457,22 @@ extern "C" int32_t cosmo_hip_batch_set_problem(cosmo_hip_batch* b, int64_t k, co
     for (int t = b->hAT[k].rowptr[j]; t < b->hAT[k].rowptr[j + 1]; ++t) { PT.col.push_back(b->hAT[k].col[t] + (int)n); PT.val.push_back(b->hAT[k].val[t]); }
   }
   PT.rowptr[n] = (int)PT.col.size();
+  { // where every stored entry of the three copies comes from in [P_nzval | A_nzval] (value_maps.h places the entries as bcsc and the loop above do)
+    std::vector<int> prp, pmap, arp, amap, mrp, msp, mmap;
+    if (value_map_csr(n, n, P_colptr, P_rowval, prp, pmap) || value_map_csr(m, n, A_colptr, A_rowval, arp, amap))
+      return bfail(b, COSMO_HIP_ERR_INVALID, "batch_set_problem: malformed CSC pattern");
+    value_map_merged(n, prp, pmap, A_colptr, mrp, msp, mmap);
+    const int32_t nnzP = (int32_t)pmap.size();
+    if (mrp != PT.rowptr || msp != PT.split || arp != b->hA[k].rowptr) return bfail(b, COSMO_HIP_ERR_INVALID, "batch_set_problem: value maps and staged copies differ");
+    b->um_nnzP[k] = nnzP; b->um_nnzA[k] = (long long)amap.size();
+    std::vector<int32_t>& uA = b->um_A[k]; std::vector<int32_t>& uPT = b->um_PT[k];
+    uA.resize(amap.size()); uPT.resize(mmap.size());
+    for (size_t t = 0; t < amap.size(); ++t) uA[t] = nnzP + amap[t];
+    for (int64_t j = 0; j < n; ++j) {
+      for (int t = mrp[j]; t < msp[j]; ++t) uPT[(size_t)t] = mmap[(size_t)t];
+      for (int t = msp[j]; t < mrp[j + 1]; ++t) uPT[(size_t)t] = nnzP + mmap[(size_t)t];
+    }
+  }
   std::copy(q, q + n, b->hq.begin() + (size_t)k * n);
   std::copy(bvec, bvec + m, b->hb.begin() + (size_t)k * m);
   b->have[k] = 1;
@@ -2686,13 +2755,18 @@ static int32_t build_lds_images(cosmo_hip_batch* b) {
     uint32_t* Tpr = reinterpret_cast<uint32_t*>(im.data() + h.oTpr);
     unsigned short* Prp = reinterpret_cast<unsigned short*>(im.data() + h.oPrp);
     unsigned short* Pcol = reinterpret_cast<unsigned short*>(im.data() + h.oPcol);
+    // source index of every slot of Aval / Pval (cosmo_hip_batch_stage_matrices), carried through every reordering below next to the values
+    std::vector<int32_t>& srcA = b->um_imgA[(size_t)k]; std::vector<int32_t>& srcP = b->um_imgP[(size_t)k];
+    const std::vector<int32_t>& uA = b->um_A[(size_t)k]; const std::vector<int32_t>& uPT = b->um_PT[(size_t)k];
+    srcA.assign(uA.begin(), uA.end()); srcP.assign((size_t)nnzP, -1);
+    b->um_imgA2[(size_t)k].clear(); b->um_pd[(size_t)k].clear();
     for (long long t = 0; t < nnzA; ++t) { Aval[t] = A.val[t]; Acol[t] = (unsigned short)A.col[t]; }
     for (long long i = 0; i <= m; ++i) Arp[i] = (unsigned short)A.rowptr[i];
     std::vector<int> cur(A.rowptr.begin(), A.rowptr.end() - 1);
     long long pp = 0;
     for (long long j = 0; j < n; ++j) {
       Trp[j] = (unsigned short)AT.rowptr[j]; Prp[j] = (unsigned short)pp;
-      for (int t = PT.rowptr[j]; t < PT.split[j]; ++t) { Pval[pp] = PT.val[t]; Pcol[pp] = (unsigned short)PT.col[t]; ++pp; }
+      for (int t = PT.rowptr[j]; t < PT.split[j]; ++t) { Pval[pp] = PT.val[t]; Pcol[pp] = (unsigned short)PT.col[t]; srcP[(size_t)pp] = uPT[(size_t)t]; ++pp; }
       for (int t = AT.rowptr[j]; t < AT.rowptr[j + 1]; ++t) {
         const int i = AT.col[t]; const int p = cur[i]++;
         if (p >= A.rowptr[i + 1] || A.col[p] != (int)j || A.val[p] != AT.val[t]) return bfail(b, COSMO_HIP_ERR_INVALID, "LDS image: A / A' mismatch");
@@ -2710,11 +2784,12 @@ static int32_t build_lds_images(cosmo_hip_batch* b) {
       std::vector<unsigned short> nAcol((size_t)nnzA), nPcol((size_t)nnzP);
       std::vector<uint32_t> nTpr((size_t)nnzA);
       std::vector<int> newstart((size_t)m);
+      std::vector<int32_t> nsrcA((size_t)nnzA), nsrcP((size_t)nnzP);
       long long wq = 0;
       for (long long q = 0; q < m; ++q) {
         const int r = gordA[(size_t)q];
         newstart[(size_t)r] = (int)wq;
-        for (int t = A.rowptr[r]; t < A.rowptr[r + 1]; ++t) { nAval[(size_t)wq] = Aval[t]; nAcol[(size_t)wq] = Acol[t]; ++wq; }
+        for (int t = A.rowptr[r]; t < A.rowptr[r + 1]; ++t) { nAval[(size_t)wq] = Aval[t]; nAcol[(size_t)wq] = Acol[t]; nsrcA[(size_t)wq] = srcA[(size_t)t]; ++wq; }
       }
       long long wt = 0, wp = 0;
       for (long long q = 0; q < n; ++q) {
@@ -2723,8 +2798,9 @@ static int32_t build_lds_images(cosmo_hip_batch* b) {
           const uint32_t pr = Tpr[t]; const int row = (int)(pr >> 16), pold = (int)(pr & 0xffffu);
           nTpr[(size_t)wt++] = (uint32_t)(newstart[(size_t)row] + (pold - A.rowptr[row])) | ((uint32_t)row << 16);
         }
-        for (int t = Prp[c]; t < Prp[c + 1]; ++t) { nPval[(size_t)wp] = Pval[t]; nPcol[(size_t)wp] = Pcol[t]; ++wp; }
+        for (int t = Prp[c]; t < Prp[c + 1]; ++t) { nPval[(size_t)wp] = Pval[t]; nPcol[(size_t)wp] = Pcol[t]; nsrcP[(size_t)wp] = srcP[(size_t)t]; ++wp; }
       }
+      srcA.swap(nsrcA); srcP.swap(nsrcP);
       std::copy(nAval.begin(), nAval.end(), Aval); std::copy(nAcol.begin(), nAcol.end(), Acol);
       std::copy(nTpr.begin(), nTpr.end(), Tpr); std::copy(nPval.begin(), nPval.end(), Pval); std::copy(nPcol.begin(), nPcol.end(), Pcol);
       for (long long q = 0; q <= m; ++q) Arp[q] = (unsigned short)prA[(size_t)q];
@@ -2771,12 +2847,13 @@ static int32_t build_lds_images(cosmo_hip_batch* b) {
         if (b->h_qposA.empty()) b->h_qposA.assign((size_t)b->nprob * m, 0);
         std::vector<real> nAval((size_t)nnzA); std::vector<unsigned short> nAcol((size_t)nnzA), nArp((size_t)m + 1);
         std::vector<int> newstart((size_t)m);
+        std::vector<int32_t> nsrcA((size_t)nnzA), nsrcP((size_t)nnzP);
         long long w = 0;
         for (long long q = 0; q < m; ++q) {
           const int r = ordA[(size_t)q];
           nArp[(size_t)q] = (unsigned short)w; newstart[(size_t)r] = (int)w;
           b->h_qposA[(size_t)k * m + (size_t)r] = (int)q;
-          for (int t = A.rowptr[r]; t < A.rowptr[r + 1]; ++t) { nAval[(size_t)w] = Aval[t]; nAcol[(size_t)w] = Acol[t]; ++w; }
+          for (int t = A.rowptr[r]; t < A.rowptr[r + 1]; ++t) { nAval[(size_t)w] = Aval[t]; nAcol[(size_t)w] = Acol[t]; nsrcA[(size_t)w] = srcA[(size_t)t]; ++w; }
         }
         nArp[(size_t)m] = (unsigned short)w;
         std::vector<uint32_t> nTpr((size_t)nnzA); std::vector<unsigned short> nTrp((size_t)n + 1), nPrp((size_t)n + 1), nPcol((size_t)nnzP);
@@ -2789,8 +2866,9 @@ static int32_t build_lds_images(cosmo_hip_batch* b) {
             const uint32_t pr = Tpr[t]; const int row = (int)(pr >> 16), pold = (int)(pr & 0xffffu);
             nTpr[(size_t)wt++] = (uint32_t)(newstart[(size_t)row] + (pold - A.rowptr[row])) | ((uint32_t)row << 16);
           }
-          for (int t = Prp[c]; t < Prp[c + 1]; ++t) { nPval[(size_t)wp] = Pval[t]; nPcol[(size_t)wp] = Pcol[t]; ++wp; }
+          for (int t = Prp[c]; t < Prp[c + 1]; ++t) { nPval[(size_t)wp] = Pval[t]; nPcol[(size_t)wp] = Pcol[t]; nsrcP[(size_t)wp] = srcP[(size_t)t]; ++wp; }
         }
+        srcA.swap(nsrcA); srcP.swap(nsrcP);
         nTrp[(size_t)n] = (unsigned short)wt; nPrp[(size_t)n] = (unsigned short)wp;
         std::copy(nAval.begin(), nAval.end(), Aval); std::copy(nAcol.begin(), nAcol.end(), Acol); std::copy(nArp.begin(), nArp.end(), Arp);
         std::copy(nTpr.begin(), nTpr.end(), Tpr); std::copy(nTrp.begin(), nTrp.end(), Trp); std::copy(nPrp.begin(), nPrp.end(), Prp);
@@ -2911,6 +2989,8 @@ static int32_t build_lds_images(cosmo_hip_batch* b) {
           unsigned short* Acol2s = reinterpret_cast<unsigned short*>(i2.data() + h2.oAcol);
           uint32_t* Tpr2s = reinterpret_cast<uint32_t*>(i2.data() + h2.oTpr);
           std::vector<long long> newpos((size_t)std::max<long long>(nnzA, 1), 0);
+          std::vector<int32_t>& srcA2 = b->um_imgA2[(size_t)k];
+          srcA2.assign((size_t)nS, -1);                                                  // (the zero padding has no source)
           for (int j = 0; j < 2; ++j) for (int sx = 0; sx < 16; ++sx) for (int l = 0; l < 32; ++l) {
             const int t = 32 * sx + l, q = qA(j, t);
             const long long off = offA[j * 16 + sx] + l;
@@ -2918,7 +2998,7 @@ static int32_t build_lds_images(cosmo_hip_batch* b) {
             b->h_slA[((size_t)k * 2 + (size_t)j) * 512 + (size_t)t] = (uint32_t)off | ((uint32_t)len << 16);
             for (long long tt = 0; tt < len; ++tt) {
               const long long e = off + 32 * tt;
-              Aval2[e] = Aval[start + tt]; Acol2s[e] = (unsigned short)(Acol[start + tt] * (unsigned)sizeof(real)); newpos[(size_t)(start + tt)] = e;
+              Aval2[e] = Aval[start + tt]; srcA2[(size_t)e] = srcA[(size_t)(start + tt)]; Acol2s[e] = (unsigned short)(Acol[start + tt] * (unsigned)sizeof(real)); newpos[(size_t)(start + tt)] = e;
             }
           }
           for (int sx = 0; sx < 16; ++sx) for (int l = 0; l < 32; ++l) {
@@ -2936,7 +3016,8 @@ static int32_t build_lds_images(cosmo_hip_batch* b) {
             memcpy(i2.data() + h2.oPrp, Prp, (size_t)(n + 1) * 2);
             memcpy(i2.data() + h2.oPcol, Pcol, (size_t)nnzP * 2);
           } else {
-            for (long long j = 0; j < n; ++j) if (PT.split[j] > PT.rowptr[j]) { b->h_pdiag[(size_t)k * n + (size_t)j] = PT.val[PT.rowptr[j]]; b->h_pdiag_has[(size_t)k * n + (size_t)j] = 1; }
+            b->um_pd[(size_t)k].assign((size_t)n, -1);
+            for (long long j = 0; j < n; ++j) if (PT.split[j] > PT.rowptr[j]) { b->h_pdiag[(size_t)k * n + (size_t)j] = PT.val[PT.rowptr[j]]; b->h_pdiag_has[(size_t)k * n + (size_t)j] = 1; b->um_pd[(size_t)k][(size_t)j] = uPT[(size_t)PT.rowptr[j]]; }
           }
           stride2 = std::max(stride2, o2);
         }
@@ -2957,8 +3038,9 @@ static int32_t build_lds_images(cosmo_hip_batch* b) {
     if (hipFuncGetAttributes(&fa, fs) != hipSuccess || fa.sharedSizeBytes != 0) { (void)hipGetLastError(); use_sliced = false; }
   }
 #endif
-  if (use_sliced) { imgs.swap(imgs2); stride = stride2; }
-  else { b->h_slA.clear(); b->h_slT.clear(); b->h_pdiag.clear(); b->h_pdiag_has.clear(); }
+  if (use_sliced) { imgs.swap(imgs2); stride = stride2; b->um_imgA.swap(b->um_imgA2); }
+  else { b->h_slA.clear(); b->h_slT.clear(); b->h_pdiag.clear(); b->h_pdiag_has.clear(); for (auto& v : b->um_pd) v.clear(); }
+  for (auto& v : b->um_imgA2) std::vector<int32_t>().swap(v);
   b->D.sliced = use_sliced ? 1 : 0;
   unsigned char* d = nullptr;
   BHIP(b, hipMalloc((void**)&d, (size_t)stride * b->nprob));
@@ -3053,6 +3135,13 @@ extern "C" int32_t cosmo_hip_batch_set_params(cosmo_hip_batch* b, const cosmo_hi
       if ((rc = bup(b, &D.posM, b->h_posM))) return rc;
     }
   }
+  if (!b->d_img) for (int k = 0; k < nprob; ++k) { std::vector<int32_t>().swap(b->um_imgA[(size_t)k]); std::vector<int32_t>().swap(b->um_imgP[(size_t)k]); b->um_pd[(size_t)k].clear(); }
+  b->um_offA.assign((size_t)nprob, 0); b->um_offPT.assign((size_t)nprob, 0); b->um_offV.assign((size_t)nprob + 1, 0);
+  for (int k = 0; k + 1 < nprob; ++k) {                     // (the concatenation of bmat_upload)
+    b->um_offA[(size_t)k + 1] = b->um_offA[(size_t)k] + (long long)b->hA[(size_t)k].val.size();
+    b->um_offPT[(size_t)k + 1] = b->um_offPT[(size_t)k] + (long long)b->hPT[(size_t)k].val.size();
+  }
+  for (int k = 0; k < nprob; ++k) b->um_offV[(size_t)k + 1] = b->um_offV[(size_t)k] + b->um_nnzP[(size_t)k] + b->um_nnzA[(size_t)k];
   if ((rc = bmat_upload(b, b->hA, D.A, (int)m, (int)n, false))) return rc;
   if ((rc = bmat_upload(b, b->hAT, D.AT, (int)n, (int)m, false))) return rc;
   if ((rc = bmat_upload(b, b->hPT, D.PT, (int)n, (int)n, true))) return rc;
@@ -3564,10 +3653,168 @@ extern "C" int32_t cosmo_hip_batch_stage_qb(cosmo_hip_batch* b, int64_t k, const
   return COSMO_HIP_OK;
 }
 
+// ---- new values of P and A on the same pattern (include/cosmo_hip.h: cosmo_hip_batch_stage_matrices) ------------------------------------------------
+// The first staged update of the batch uploads the maps (one int32 array, member after member) and the descriptor table, and allocates the staging
+// that holds the header and the values of up to all members; no array that set_params made is touched.
+static int32_t bupd_init(cosmo_hip_batch* b) {
+  if (b->d_udesc) return COSMO_HIP_OK;
+  const int nprob = b->nprob; const long long n = b->n;
+  std::vector<int32_t> maps;
+  std::vector<long long> moff((size_t)nprob * BUPD_ND, -1);
+  auto put = [&](int k, int d, const std::vector<int32_t>& v) { if (!v.empty()) { moff[(size_t)k * BUPD_ND + d] = (long long)maps.size(); maps.insert(maps.end(), v.begin(), v.end()); } };
+  for (int k = 0; k < nprob; ++k) {
+    put(k, 0, b->um_A[(size_t)k]); put(k, 2, b->um_PT[(size_t)k]);
+    if (b->d_img) { put(k, 3, b->um_imgA[(size_t)k]); put(k, 4, b->um_imgP[(size_t)k]); if (b->D.pdiag) put(k, 5, b->um_pd[(size_t)k]); }
+  }
+  int32_t rc;
+  if ((rc = bup(b, &b->d_umap, maps))) return rc;
+  std::vector<BUpdDesc> desc((size_t)nprob * BUPD_ND);
+  std::vector<unsigned char> hd(sizeof(LdsHdr));
+  for (int k = 0; k < nprob; ++k) {
+    BUpdDesc* e = desc.data() + (size_t)k * BUPD_ND;
+    for (int d = 0; d < BUPD_ND; ++d) { e[d].dst = nullptr; e[d].map = nullptr; e[d].count = 0; e[d].base = 0; }
+    auto set = [&](int d, real* dst, long long count) {
+      const long long o = moff[(size_t)k * BUPD_ND + d];
+      if (count <= 0 || o < 0) return;
+      e[d].dst = dst; e[d].map = b->d_umap + o; e[d].count = (int)count;
+    };
+    const long long nP = b->um_nnzP[(size_t)k], nA = b->um_nnzA[(size_t)k];
+    set(0, const_cast<real*>(b->D.A.val) + b->um_offA[(size_t)k], nA);
+    if (nA > 0) { e[1].dst = const_cast<real*>(b->D.AT.val) + b->um_offA[(size_t)k]; e[1].count = (int)nA; e[1].base = (int)nP; }      // A' keeps the caller's order
+    set(2, const_cast<real*>(b->D.PT.val) + b->um_offPT[(size_t)k], nP + nA);
+    if (b->d_img) {                                           // the member's image as it lies on the device: its own header says where the values are
+      unsigned char* im = b->d_img + (size_t)k * b->img_stride;
+      BHIP(b, hipMemcpy(hd.data(), im, sizeof(LdsHdr), hipMemcpyDeviceToHost));
+      LdsHdr h; memcpy(&h, hd.data(), sizeof h);
+      if ((long long)b->um_imgA[(size_t)k].size() != h.nnzA || (h.nnzP != 0 && (long long)b->um_imgP[(size_t)k].size() != h.nnzP))
+        return bfail(b, COSMO_HIP_ERR_INVALID, "batch_stage_matrices: the image of member %d and its value maps differ in size", k);
+      set(3, reinterpret_cast<real*>(im + h.oAval), h.nnzA);
+      set(4, reinterpret_cast<real*>(im + h.oPval), h.nnzP);
+      if (b->D.pdiag) set(5, const_cast<real*>(b->D.pdiag) + (size_t)k * n, n);
+    }
+  }
+  const size_t hdr = ((size_t)nprob * sizeof(BUpdHdr) + 15) / 16 * 16;
+  if ((rc = balloc(b, &b->d_mstage, hdr + (size_t)b->um_offV[(size_t)nprob] * sizeof(real)))) return rc;
+  b->upd_map_bytes = (long long)(maps.size() * sizeof(int32_t) + desc.size() * sizeof(BUpdDesc));
+  b->mstg_slot.assign((size_t)nprob, -1);
+  return bup(b, &b->d_udesc, desc);            // (last: d_udesc marks the set-up as done)
+}
+
+// apply_scaling = 0: the values as given; 1: the batch's D, E, c are applied on the device.  Host only; a member staged twice keeps the later values.
+extern "C" int32_t cosmo_hip_batch_stage_matrices(cosmo_hip_batch* b, int64_t k, const real* P_nzval, const real* A_nzval, int32_t apply_scaling) {
+  if (!b || !b->finalized || k < 0 || k >= b->nprob) return bfail(b, COSMO_HIP_ERR_INVALID, "batch_stage_matrices: bad call (set_params first; 0 <= k < nprob)");
+  const long long nP = b->um_nnzP[(size_t)k], nA = b->um_nnzA[(size_t)k];
+  if (nP == 0) P_nzval = nullptr;
+  if (nA == 0) A_nzval = nullptr;
+  if (!P_nzval && !A_nzval) return COSMO_HIP_OK;
+  if (hipSetDevice(b->device) != hipSuccess) return bfail(b, COSMO_HIP_ERR_HIP, "hipSetDevice failed");
+  int32_t rc;
+  if ((rc = bresident_init(b)) || (rc = bupd_init(b))) return rc;
+  int32_t& slot = b->mstg_slot[(size_t)k];
+  if (slot < 0) {
+    slot = (int32_t)b->mstg_mem.size();
+    b->mstg_mem.push_back((int32_t)k); b->mstg_flag.push_back(0); b->mstg_val.emplace_back((size_t)(nP + nA), R(0.0));
+  }
+  std::vector<real>& v = b->mstg_val[(size_t)slot];
+  int32_t& f = b->mstg_flag[(size_t)slot];
+  // one scaling switch per member and launch: a part staged earlier under the other setting would be scaled twice or not at all
+  if ((f & 3) && ((f & 4) != 0) != (apply_scaling != 0)) return bfail(b, COSMO_HIP_ERR_INVALID, "batch_stage_matrices: member %d is staged with the other apply_scaling", (int)k);
+  if (P_nzval) { std::copy(P_nzval, P_nzval + nP, v.begin()); f |= 1; }
+  if (A_nzval) { std::copy(A_nzval, A_nzval + nA, v.begin() + nP); f |= 2; }
+  if (apply_scaling) f |= 4;
+  return COSMO_HIP_OK;
+}
+
+// One copy {headers | values of the staged members}, one launch; a direct batch then factorises the staged members again (their current rho).
+static int32_t bapply_matrices(cosmo_hip_batch* b) {
+  const int cnt = (int)b->mstg_mem.size();
+  if (hipSetDevice(b->device) != hipSuccess) return bfail(b, COSMO_HIP_ERR_HIP, "hipSetDevice failed");
+  const size_t hdr = ((size_t)b->nprob * sizeof(BUpdHdr) + 15) / 16 * 16;
+  size_t tot = 0;
+  for (int j = 0; j < cnt; ++j) tot += b->mstg_val[(size_t)j].size();
+  std::vector<unsigned char> buf(hdr + tot * sizeof(real), 0);
+  BUpdHdr* hh = reinterpret_cast<BUpdHdr*>(buf.data());
+  real* vv = reinterpret_cast<real*>(buf.data() + hdr);
+  long long off = 0;
+  for (int j = 0; j < cnt; ++j) {
+    const int32_t k = b->mstg_mem[(size_t)j];
+    hh[j].mem = k; hh[j].flag = b->mstg_flag[(size_t)j]; hh[j].nnzP = (int32_t)b->um_nnzP[(size_t)k]; hh[j].nnzA = (int32_t)b->um_nnzA[(size_t)k]; hh[j].off = off;
+    std::copy(b->mstg_val[(size_t)j].begin(), b->mstg_val[(size_t)j].end(), vv + off);
+    off += (long long)b->mstg_val[(size_t)j].size();
+  }
+  BHIP(b, hipMemcpyAsync(b->d_mstage, buf.data(), buf.size(), hipMemcpyHostToDevice, b->stream));
+  const BUpdHdr* dh = reinterpret_cast<const BUpdHdr*>(b->d_mstage);
+  hipLaunchKernelGGL(k_batch_update_matrices, dim3(cnt), dim3(256), 0, b->stream, b->D, dh, reinterpret_cast<real*>(b->d_mstage + hdr), b->d_udesc, b->d_D,
+                     b->d_E, b->d_c);
+  BHIP(b, hipGetLastError());
+  BHIP(b, hipStreamSynchronize(b->stream));       // (buf is pageable host memory)
+  const std::vector<int32_t> mem = b->mstg_mem;
+  for (int32_t k : b->mstg_mem) b->mstg_slot[(size_t)k] = -1;
+  b->mstg_mem.clear(); b->mstg_flag.clear(); b->mstg_val.clear();
+  b->upd_count += 1; b->upd_last_bytes = (long long)buf.size();
+  if (b->ldl) {
+    b->upd_factorisations += cnt;
+    const int32_t rc = bldl_refactor_members(b->ldl, b->D.ldl, b->stream, b->nprob, cnt, reinterpret_cast<const int*>(b->d_mstage), (int)(sizeof(BUpdHdr) / sizeof(int)),
+                                             mem.data(), (int)b->n, (int)b->m, (real)b->prm.sigma, b->D.PT.rowptr, b->D.PT.val, b->D.PT.nz_off, b->D.A.rowptr,
+                                             b->D.A.val, b->D.A.nz_off, b->D.rho, b->err);
+    if (rc) return rc;
+  }
+  return COSMO_HIP_OK;
+}
+
+extern "C" int32_t cosmo_hip_batch_apply_updates(cosmo_hip_batch* b);
+extern "C" int32_t cosmo_hip_batch_update_matrices(cosmo_hip_batch* b, int64_t count, const int64_t* members, const real* P_vals, const real* A_vals,
+                                                   int32_t apply_scaling) {
+  if (!b || !b->finalized || count < 0 || (count > 0 && !members)) return bfail(b, COSMO_HIP_ERR_INVALID, "batch_update_matrices: bad arguments (set_params first)");
+  for (int64_t j = 0; j < count; ++j) if (members[j] < 0 || members[j] >= b->nprob) return bfail(b, COSMO_HIP_ERR_INVALID, "batch_update_matrices: member out of range");
+  size_t po = 0, ao = 0;                           // the value arrays are concatenated per listed member
+  for (int64_t j = 0; j < count; ++j) {
+    const int64_t k = members[j];
+    const int32_t rc = cosmo_hip_batch_stage_matrices(b, k, P_vals ? P_vals + po : nullptr, A_vals ? A_vals + ao : nullptr, apply_scaling);
+    if (rc) return rc;
+    po += (size_t)b->um_nnzP[(size_t)k]; ao += (size_t)b->um_nnzA[(size_t)k];
+  }
+  return cosmo_hip_batch_apply_updates(b);
+}
+
+// out = {updates applied, destination arrays refreshed per update, host rebuilds (0: there is no such path), bytes uploaded by the last update, device
+// bytes held by the maps, factorisations caused by updates, 0, 0}
+extern "C" int32_t cosmo_hip_batch_update_matrices_info(cosmo_hip_batch* b, int64_t out[8]) {
+  if (!b || !out || !b->finalized) return bfail(b, COSMO_HIP_ERR_INVALID, "batch_update_matrices_info: set_params first");
+  out[0] = b->upd_count; out[1] = 3 + (b->d_img ? 2 : 0) + (b->ldl ? 1 : 0); out[2] = 0; out[3] = b->upd_last_bytes; out[4] = b->upd_map_bytes;
+  out[5] = b->upd_factorisations; out[6] = 0; out[7] = 0;
+  return COSMO_HIP_OK;
+}
+
+// The device copy of member k's values: which = 0 the CSR of A, 1 the CSR of A' (the caller's CSC order), 2 the rows of [P | A'] (nnzP + nnzA values)
+extern "C" int32_t cosmo_hip_batch_get_matrix_values(cosmo_hip_batch* b, int64_t k, int32_t which, real* out) {
+  if (!b || !b->finalized || k < 0 || k >= b->nprob || which < 0 || which > 2 || !out) return bfail(b, COSMO_HIP_ERR_INVALID, "batch_get_matrix_values: bad call");
+  if (hipSetDevice(b->device) != hipSuccess) return bfail(b, COSMO_HIP_ERR_HIP, "hipSetDevice failed");
+  const long long nP = b->um_nnzP[(size_t)k], nA = b->um_nnzA[(size_t)k];
+  const real* src = which == 0 ? b->D.A.val + b->um_offA[(size_t)k] : (which == 1 ? b->D.AT.val + b->um_offA[(size_t)k] : b->D.PT.val + b->um_offPT[(size_t)k]);
+  const long long cntv = which == 2 ? nP + nA : nA;
+  if (cntv > 0) BHIP(b, hipMemcpy(out, src, (size_t)cntv * sizeof(real), hipMemcpyDeviceToHost));
+  return COSMO_HIP_OK;
+}
+
+// The raw bytes of member k's LDS image (none for a streaming or direct batch) followed by its row of pdiag (n values, where P lives in registers).
+// *bytes_out: their size; they are written to out if capacity holds them (out may be NULL to ask for the size).
+extern "C" int32_t cosmo_hip_batch_get_image(cosmo_hip_batch* b, int64_t k, void* out, int64_t capacity, int64_t* bytes_out) {
+  if (!b || !b->finalized || k < 0 || k >= b->nprob || !bytes_out) return bfail(b, COSMO_HIP_ERR_INVALID, "batch_get_image: bad call");
+  if (hipSetDevice(b->device) != hipSuccess) return bfail(b, COSMO_HIP_ERR_HIP, "hipSetDevice failed");
+  const size_t ib = b->d_img ? (size_t)b->img_stride : 0, pb = (b->d_img && b->D.pdiag) ? (size_t)b->n * sizeof(real) : 0;
+  *bytes_out = (int64_t)(ib + pb);
+  if (!out) return COSMO_HIP_OK;
+  if (capacity < (int64_t)(ib + pb)) return bfail(b, COSMO_HIP_ERR_INVALID, "batch_get_image: capacity %lld < %lld bytes", (long long)capacity, (long long)(ib + pb));
+  if (ib) BHIP(b, hipMemcpy(out, b->d_img + (size_t)k * b->img_stride, ib, hipMemcpyDeviceToHost));
+  if (pb) BHIP(b, hipMemcpy((unsigned char*)out + ib, b->D.pdiag + (size_t)k * b->n, pb, hipMemcpyDeviceToHost));
+  return COSMO_HIP_OK;
+}
+
 extern "C" int32_t cosmo_hip_batch_apply_updates(cosmo_hip_batch* b) {
   if (!b || !b->finalized) return bfail(b, COSMO_HIP_ERR_INVALID, "batch_apply_updates: set_params first");
   const int cnt = (int)b->stg_mem.size();
-  if (cnt == 0) return COSMO_HIP_OK;
+  if (cnt == 0) return b->mstg_mem.empty() ? COSMO_HIP_OK : bapply_matrices(b);
   if (hipSetDevice(b->device) != hipSuccess) return bfail(b, COSMO_HIP_ERR_HIP, "hipSetDevice failed");
   // one copy: {members, flags} (int32 each, padded to 16 bytes) followed by the n + m raw values of every staged member
   const size_t N = (size_t)(b->n + b->m), hdr = ((size_t)2 * cnt * sizeof(int32_t) + 15) / 16 * 16, bytes = hdr + (size_t)cnt * N * sizeof(real);
@@ -3584,7 +3831,7 @@ extern "C" int32_t cosmo_hip_batch_apply_updates(cosmo_hip_batch* b) {
   BHIP(b, hipStreamSynchronize(b->stream));       // (buf is pageable host memory)
   for (int32_t k : b->stg_mem) b->stg_slot[(size_t)k] = -1;
   b->stg_mem.clear(); b->stg_flag.clear(); b->stg_val.clear();
-  return COSMO_HIP_OK;
+  return b->mstg_mem.empty() ? COSMO_HIP_OK : bapply_matrices(b);
 }
 
 extern "C" int32_t cosmo_hip_batch_update_qb(cosmo_hip_batch* b, int64_t count, const int64_t* members, const real* q, const real* bvec) {

@@ -34,6 +34,9 @@ struct GProblem {
   double cinv = 1.0, c = 0.0;     // c: set_scaling_full's (0: 1 / cinv)
   std::vector<real> uq, ub;       // raw q / b staged for a member on its own handle (cosmo_hip_batch_group_stage_qb)
   bool have_uq = false, have_ub = false;
+  long long nnzP = 0, nnzA = 0;   // stored entries (set_problem; Px / Ax are released by set_params)
+  std::vector<real> uP, uA;       // new values of P / A staged for a member on its own handle (cosmo_hip_batch_group_stage_matrices)
+  bool have_uP = false, have_uA = false; int32_t u_scale = 0;
   bool have = false, have_cones = false, have_scaling = false, have_x0 = false, have_s0 = false, have_mu0 = false;
   bool dev_scaling = false;       // the scaling is the device pass's (cosmo_hip_batch_group_set_device_scaling), not the caller's
   int cls = -1, pos = -1;         // class and position inside the class
@@ -106,6 +109,7 @@ extern "C" int32_t cosmo_hip_batch_group_set_problem(cosmo_hip_batch_group* g, i
   p.n = n; p.m = m;
   const int64_t nnzP = P_colptr[n] - 1, nnzA = A_colptr[n] - 1;
   if (nnzP < 0 || nnzA < 0) return gfail(g, COSMO_HIP_ERR_INVALID, "batch_group_set_problem: bad colptr");
+  p.nnzP = nnzP; p.nnzA = nnzA;
   p.Pp.assign(P_colptr, P_colptr + n + 1); p.Pi.assign(P_rowval, P_rowval + nnzP); p.Px.assign(P_nzval, P_nzval + nnzP);
   p.Ap.assign(A_colptr, A_colptr + n + 1); p.Ai.assign(A_rowval, A_rowval + nnzA); p.Ax.assign(A_nzval, A_nzval + nnzA);
   p.q.assign(q, q + n); p.b.assign(bvec, bvec + m);
@@ -548,6 +552,21 @@ extern "C" int32_t cosmo_hip_batch_group_stage_qb(cosmo_hip_batch_group* g, int6
   return COSMO_HIP_OK;
 }
 
+extern "C" int32_t cosmo_hip_batch_group_stage_matrices(cosmo_hip_batch_group* g, int64_t k, const real* P_nzval, const real* A_nzval, int32_t apply_scaling) {
+  GCHECK(g, k);
+  if (!g->finalized) return gfail(g, COSMO_HIP_ERR_INVALID, "batch_group_stage_matrices: set_params first");
+  GProblem& p = g->prob[(size_t)k];
+  GClass& C = g->cls[(size_t)p.cls];
+  if (C.b) {
+    const int32_t rc = cosmo_hip_batch_stage_matrices(C.b, p.pos, P_nzval, A_nzval, apply_scaling);
+    return rc ? gfail(g, rc, std::string("batch_stage_matrices: ") + cosmo_hip_batch_last_error(C.b)) : COSMO_HIP_OK;
+  }
+  if (P_nzval) { p.uP.assign(P_nzval, P_nzval + p.nnzP); p.have_uP = true; }
+  if (A_nzval) { p.uA.assign(A_nzval, A_nzval + p.nnzA); p.have_uA = true; }
+  p.u_scale = apply_scaling;
+  return COSMO_HIP_OK;
+}
+
 // D, E, c of a problem: set_scaling_full's own values, else the reciprocals of the inverses (as cosmo_hip_set_scaling recovers them)
 static real gscale_D(const GProblem& p, long long i) { return p.Dsc.empty() ? R(1.0) / p.Dinv[(size_t)i] : p.Dsc[(size_t)i]; }
 static real gscale_E(const GProblem& p, long long i) { return p.Esc.empty() ? R(1.0) / p.Einv[(size_t)i] : p.Esc[(size_t)i]; }
@@ -563,6 +582,12 @@ extern "C" int32_t cosmo_hip_batch_group_apply_updates(cosmo_hip_batch_group* g)
     }
     for (size_t j = 0; j < C.members.size(); ++j) {
       GProblem& p = g->prob[(size_t)C.members[j]];
+      if (p.have_uP || p.have_uA) {                      // (the handle holds its own D, E, c: cosmo_hip_set_scaling_full / cosmo_hip_scale_ruiz)
+        const int32_t rc = cosmo_hip_update_matrices(C.hs[j], p.have_uP ? p.uP.data() : nullptr, p.have_uA ? p.uA.data() : nullptr, p.u_scale);
+        p.have_uP = p.have_uA = false;
+        std::vector<real>().swap(p.uP); std::vector<real>().swap(p.uA);
+        if (rc) return gfail(g, rc, std::string("update_matrices of problem ") + std::to_string(C.members[j]) + ": " + cosmo_hip_last_error(C.hs[j]));
+      }
       if (!p.have_uq && !p.have_ub) continue;
       std::vector<real> qs, bs;                         // update! (src/interface.jl:196-208) with the scaled problem's D, E, c
       if (p.have_uq) { qs.resize((size_t)p.n); const real c = p.have_scaling ? gscale_c(p) : R(1.0); for (long long i = 0; i < p.n; ++i) qs[(size_t)i] = p.have_scaling ? (gscale_D(p, i) * p.uq[(size_t)i]) * c : p.uq[(size_t)i]; }

@@ -117,6 +117,12 @@ int32_t bldl_build(int nprob, long long n, long long m, const std::vector<HostCs
 // The first factorisation of every member and the inertia check (nnz(D > 0) == n, kktsolver.jl:304).  PT / A: the batch's device matrices.
 int32_t bldl_setup_factor(BLdlPlan* p, const BLdlDev& dev, hipStream_t st, int nprob, int n, int m, real sigma, const int* PT_rowptr, const real* PT_val,
                           const long long* PT_nzoff, const int* A_rowptr, const real* A_val, const long long* A_nzoff, const real* rho, std::string& err);
+// The same for `count` listed members only, on the kept analysis with their current rho (new matrix values: cosmo_hip_batch_apply_updates).  d_mem: the
+// device list, member j at d_mem[j * stride]; h_mem: its host copy.  A listed member's pivot flag is cleared first, so a valid update restores a member
+// that failed before.  INVALID names the first listed member that fails the pivot or the inertia check; the others are factorised all the same.
+int32_t bldl_refactor_members(BLdlPlan* p, const BLdlDev& dev, hipStream_t st, int nprob, int count, const int* d_mem, int stride, const int* h_mem, int n, int m,
+                              real sigma, const int* PT_rowptr, const real* PT_val, const long long* PT_nzoff, const int* A_rowptr, const real* A_val,
+                              const long long* A_nzoff, const real* rho, std::string& err);
 // out = {nnz(L), panel reals per problem, supernodes, tree height, widest supernode, analysis ns, factorisations (all members), min positive pivots}
 int32_t bldl_info(BLdlPlan* p, const BLdlDev& dev, hipStream_t st, int nprob, int64_t* out, std::string& err);
 int32_t bldl_counts(BLdlPlan* p, const BLdlDev& dev, hipStream_t st, int nprob, int64_t* out, std::string& err);

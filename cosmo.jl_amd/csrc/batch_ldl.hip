@@ -152,6 +152,35 @@ int32_t bldl_setup_factor(BLdlPlan* p, const BLdlDev& dev, hipStream_t st, int n
   return COSMO_HIP_OK;
 }
 
+// k_bldl_setup for a list of members (cosmo_hip_batch_apply_updates after new matrix values): block j refactors member mem[j * stride] with its current rho
+__global__ __launch_bounds__(COSMO_BS) void k_bldl_setup_members(BLdlDev L, int n, int m, real sigma, const int* __restrict__ mem, int stride,
+                                                                 const int* __restrict__ PT_rowptr, const real* __restrict__ PT_val,
+                                                                 const long long* __restrict__ PT_nzoff, const int* __restrict__ A_rowptr,
+                                                                 const real* __restrict__ A_val, const long long* __restrict__ A_nzoff, const real* __restrict__ rho) {
+  const int k = mem[(long long)blockIdx.x * stride];
+  const int pnnz = PT_rowptr[(long long)k * (n + 1) + n], annz = A_rowptr[(long long)k * (m + 1) + m];
+  if (threadIdx.x == 0) L.fail[k] = 0;                                     // (a member that failed before gets a fresh verdict; refill_factor synchronises first)
+  (void)bldl_refill_factor<COSMO_BS>(L, k, n, m, sigma, PT_val + PT_nzoff[k], pnnz, A_val + A_nzoff[k], annz, rho + (long long)k * m, PT_nzoff[k], A_nzoff[k]);
+}
+
+int32_t bldl_refactor_members(BLdlPlan*, const BLdlDev& dev, hipStream_t st, int nprob, int count, const int* d_mem, int stride, const int* h_mem, int n, int m, real sigma,
+                              const int* PT_rowptr, const real* PT_val, const long long* PT_nzoff, const int* A_rowptr, const real* A_val,
+                              const long long* A_nzoff, const real* rho, std::string& err) {
+  if (count <= 0) return COSMO_HIP_OK;
+  hipLaunchKernelGGL(k_bldl_setup_members, dim3(count), dim3(COSMO_BS), 0, st, dev, n, m, sigma, d_mem, stride, PT_rowptr, PT_val, PT_nzoff, A_rowptr, A_val,
+                     A_nzoff, rho);
+  if (hipGetLastError() != hipSuccess || hipStreamSynchronize(st) != hipSuccess) { err = "direct batch: the factorisation of the updated members failed to run"; return COSMO_HIP_ERR_HIP; }
+  std::vector<int> npos((size_t)nprob), fail((size_t)nprob);
+  if (hipMemcpy(npos.data(), dev.npos, sizeof(int) * nprob, hipMemcpyDeviceToHost) != hipSuccess ||
+      hipMemcpy(fail.data(), dev.fail, sizeof(int) * nprob, hipMemcpyDeviceToHost) != hipSuccess) { err = "direct batch: hipMemcpy failed"; return COSMO_HIP_ERR_HIP; }
+  for (int j = 0; j < count; ++j) {
+    const int k = h_mem[j], pos = npos[(size_t)k], bad = fail[(size_t)k];
+    if (bad) { err = "direct KKT solver: zero or non-finite pivot in the LDL' factorisation (member " + std::to_string(k) + ")"; return COSMO_HIP_ERR_INVALID; }
+    if (pos != n) { err = "Objective function is not convex. (member " + std::to_string(k) + ")"; return COSMO_HIP_ERR_INVALID; }
+  }
+  return COSMO_HIP_OK;
+}
+
 int32_t bldl_info(BLdlPlan* p, const BLdlDev& dev, hipStream_t st, int nprob, int64_t* out, std::string& err) {
   std::vector<int> nf((size_t)nprob), pos((size_t)nprob);
   if (hipStreamSynchronize(st) != hipSuccess || hipMemcpy(nf.data(), dev.nfact, sizeof(int) * nprob, hipMemcpyDeviceToHost) != hipSuccess ||

@@ -480,6 +480,39 @@ function batch_get_qb(::Type{T}, b::Ptr{Cvoid}, k::Integer, n::Integer, m::Integ
     _rcheck(ccall((:cosmo_hip_batch_get_qb, libpath(T)), Int32, (Ptr{Cvoid}, Int64, Ptr{T}, Ptr{T}), b, Int64(k), q, bv), "cosmo_hip_batch_get_qb")
     return q, bv
 end
+# new VALUES of P / A of a member on the same pattern (the order of set_problem's nzval arrays; `nothing` leaves a matrix alone), applied by
+# batch_apply_updates!; apply_scaling = true: the device applies the batch's D, E, c to the raw values
+function batch_stage_matrices!(::Type{T}, b::Ptr{Cvoid}, k::Integer, Pv::Union{Vector{T}, Nothing}, Av::Union{Vector{T}, Nothing}, apply_scaling::Bool) where {T <: HipFloat}
+    GC.@preserve Pv Av _rcheck(ccall((:cosmo_hip_batch_stage_matrices, libpath(T)), Int32, (Ptr{Cvoid}, Int64, Ptr{T}, Ptr{T}, Int32), b, Int64(k), _rptr(Pv), _rptr(Av),
+                                     Int32(apply_scaling)), "cosmo_hip_batch_stage_matrices")
+end
+function batch_update_matrices!(::Type{T}, b::Ptr{Cvoid}, members::Vector{Int64}, Pv::Union{Vector{T}, Nothing}, Av::Union{Vector{T}, Nothing}, apply_scaling::Bool) where {T <: HipFloat}
+    GC.@preserve members Pv Av _rcheck(ccall((:cosmo_hip_batch_update_matrices, libpath(T)), Int32, (Ptr{Cvoid}, Int64, Ptr{Int64}, Ptr{T}, Ptr{T}, Int32),
+                                             b, Int64(length(members)), members, _rptr(Pv), _rptr(Av), Int32(apply_scaling)), "cosmo_hip_batch_update_matrices")
+end
+function batch_update_matrices_info(::Type{T}, b::Ptr{Cvoid}) where {T <: HipFloat}
+    out = zeros(Int64, 8)
+    _rcheck(ccall((:cosmo_hip_batch_update_matrices_info, libpath(T)), Int32, (Ptr{Cvoid}, Ptr{Int64}), b, out), "cosmo_hip_batch_update_matrices_info")
+    return out
+end
+function batch_get_matrix_values(::Type{T}, b::Ptr{Cvoid}, k::Integer, which::Integer, count::Integer) where {T <: HipFloat}
+    out = zeros(T, count)
+    _rcheck(ccall((:cosmo_hip_batch_get_matrix_values, libpath(T)), Int32, (Ptr{Cvoid}, Int64, Int32, Ptr{T}), b, Int64(k), Int32(which), out), "cosmo_hip_batch_get_matrix_values")
+    return out
+end
+function batch_get_image(::Type{T}, b::Ptr{Cvoid}, k::Integer) where {T <: HipFloat}
+    nb = Ref{Int64}(0)
+    _rcheck(ccall((:cosmo_hip_batch_get_image, libpath(T)), Int32, (Ptr{Cvoid}, Int64, Ptr{Cvoid}, Int64, Ref{Int64}), b, Int64(k), C_NULL, Int64(0), nb), "cosmo_hip_batch_get_image")
+    out = zeros(UInt8, nb[])
+    isempty(out) && return out
+    GC.@preserve out _rcheck(ccall((:cosmo_hip_batch_get_image, libpath(T)), Int32, (Ptr{Cvoid}, Int64, Ptr{Cvoid}, Int64, Ref{Int64}), b, Int64(k), pointer(out), Int64(length(out)), nb),
+                             "cosmo_hip_batch_get_image")
+    return out
+end
+function batch_group_stage_matrices!(::Type{T}, g::Ptr{Cvoid}, k::Integer, Pv::Union{Vector{T}, Nothing}, Av::Union{Vector{T}, Nothing}, apply_scaling::Bool) where {T <: HipFloat}
+    GC.@preserve Pv Av _rcheck(ccall((:cosmo_hip_batch_group_stage_matrices, libpath(T)), Int32, (Ptr{Cvoid}, Int64, Ptr{T}, Ptr{T}, Int32), g, Int64(k), _rptr(Pv), _rptr(Av),
+                                     Int32(apply_scaling)), "cosmo_hip_batch_group_stage_matrices")
+end
 # device Ruiz equilibration of a staged batch (csrc/batch_ruiz.hip): after set_problem / set_cones, before set_params, instead of set_scaling*
 batch_scale_ruiz!(::Type{T}, b::Ptr{Cvoid}, iterations::Integer, min_scaling::Real, max_scaling::Real) where {T <: HipFloat} =
     _rcheck(ccall((:cosmo_hip_batch_scale_ruiz, libpath(T)), Int32, (Ptr{Cvoid}, Int64, Cdouble, Cdouble), b, Int64(iterations), Float64(min_scaling), Float64(max_scaling)),

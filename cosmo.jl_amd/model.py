@@ -668,7 +668,8 @@ def update(model: Model, q=None, b=None, P=None, A=None):
     (cosmo_hip_update_matrices), so the next optimize() is a warm re-solve.  P / A: anything `Model.set` accepts; converted to CSC with sorted
     indices, and the stored pattern (indptr, indices) must equal the model's, else ValueError.  Explicit zeros count as stored entries: pass a
     sparse matrix that keeps them (a dense array drops the zeros of its pattern).  The Ruiz scaling is frozen: if the values change by
-    orders of magnitude, assemble a new model instead."""
+    orders of magnitude, assemble a new model instead.  On a member of a `BatchSolver` the new values are staged like q and b and applied by
+    the batch's next optimize() (cosmo_hip_batch_stage_matrices); before its first optimize() only the host data change."""
     if not model.is_assembled:
         raise RuntimeError("Model has to be assembled once before one can start updating q or b.")
     if q is not None:
@@ -689,9 +690,9 @@ def update(model: Model, q=None, b=None, P=None, A=None):
             continue
         if getattr(model, "chordal", None) is not None:
             raise RuntimeError("Problem matrix %s can not be updated if the model has been chordally decomposed before." % name)
-        if rb is not None:
-            raise NotImplementedError("update(P=, A=): a member of a resident batch (BatchSolver) takes new q and b only; close the batch or "
-                                      "solve the model on its own")
+        if rb is not None and not isinstance(rb[0], BatchSolver):
+            raise NotImplementedError("update(P=, A=): the model's resident binding is not a BatchSolver (%s): only a BatchSolver stages new matrix "
+                                      "values for its members" % type(rb[0]).__name__)
     if P is not None:
         P = _same_pattern_csc(model, P, "P")
     if A is not None:
@@ -714,7 +715,9 @@ def update(model: Model, q=None, b=None, P=None, A=None):
             model.P = P
         if A is not None:
             model.A = A
-        if model.handle is not None:
+        if rb is not None:                                        # a member of a BatchSolver: applied by its next optimize(), as q and b
+            rb[0]._stage_matrices(rb[1], None if P is None else P.data, None if A is None else A.data, on_device)
+        elif model.handle is not None:
             model.handle.update_matrices(None if P is None else P.data, None if A is None else A.data, apply_scaling=on_device)
     if rb is not None:
         rb[0]._stage(rb[1], q, b)                                 # a member of a BatchSolver: the raw vectors, scaled by the device update pass
@@ -1208,8 +1211,9 @@ class BatchSolver:
     """A batch of models that stays on the MI355X across solves (the repeated-solve workloads: MPC, parameter sweeps, online re-solves).
 
     The first `optimize()` sets the batch up as `optimize_batch` does (host Ruiz scaling, upload; a mixed list becomes a batch group) and keeps it.
-    `update(model, q=..., b=...)` on a member stages its raw vectors; the next `optimize()` applies all staged changes in one copy and one launch
-    (csrc/batch.hip: k_batch_update_qb) and re-solves with the reference's second `optimize!` (src/setup.jl:18-62): no re-scaling, every rho vector and
+    `update(model, q=..., b=...)` on a member stages its raw vectors, `update(model, P=..., A=...)` new values on the same sparsity pattern; the next
+    `optimize()` applies all staged changes in one copy and one launch each (csrc/batch.hip: k_batch_update_qb, k_batch_update_matrices; a direct
+    batch factorises the changed members again) and re-solves with the reference's second `optimize!` (src/setup.jl:18-62): no re-scaling, every rho vector and
     KKT factor kept, the accelerator restarted, status / iteration count / certificates / time limit fresh, and the iterates warm-started from the batch's
     own final ones on the device (warm_start="device") or from the models' x, s, mu (warm_start="models", e.g. after warm_start_primal).
     Results are written back to the models as `optimize_batch` does.  `close()` releases the device batch and unbinds the models."""
@@ -1244,6 +1248,11 @@ class BatchSolver:
             return                                        # not on the device yet: the first optimize uploads the model's q / b
         self._B.stage_qb(k, q, b)
 
+    def _stage_matrices(self, k, P_vals, A_vals, apply_scaling):
+        if self._B is None:
+            return                                        # not on the device yet: the first optimize uploads the model's P / A
+        self._B.stage_matrices(k, P_vals, A_vals, apply_scaling=apply_scaling)
+
     def optimize(self, warm_start: str = "device") -> List[Result]:
         import time
         if warm_start not in ("device", "models"):
@@ -1259,7 +1268,7 @@ class BatchSolver:
             self.last_times = dict(setup_s=time.perf_counter() - t0)
         else:
             B = self._B
-            B.apply_updates()                             # every staged q / b: one copy and one launch per batch
+            B.apply_updates()                             # every staged q / b and P / A: one copy and one launch each per batch
             t1 = time.perf_counter()
             if warm_start == "device":
                 B.warm_restart()

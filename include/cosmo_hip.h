@@ -283,7 +283,8 @@ COSMO_HIP_API int32_t cosmo_hip_update_qb(cosmo_hip_handle* h, const cosmo_hip_r
  * scaling is FROZEN: values that change by orders of magnitude want a new set-up.  With kkt_kind DIRECT the factor is recomputed on the
  * kept analysis and its inertia checked: an indefinite P fails with COSMO_HIP_ERR_INVALID ("Objective function is not convex.") exactly
  * as a failed cosmo_hip_update_rho does, and a later valid update or set_params restores the handle.  Row-sharded handles:
- * COSMO_HIP_ERR_UNSUPPORTED.  Batches and groups have no counterpart. */
+ * COSMO_HIP_ERR_UNSUPPORTED.  A member of a resident batch or group takes new values through cosmo_hip_batch_stage_matrices /
+ * cosmo_hip_batch_group_stage_matrices. */
 COSMO_HIP_API int32_t cosmo_hip_update_matrices(cosmo_hip_handle* h, const cosmo_hip_real* P_nzval, const cosmo_hip_real* A_nzval, int32_t apply_scaling);
 /* out = {updates applied, derived value arrays refreshed on the device (count over all updates), host rebuilds of the KKT route
  * caused by updates (0: every route is refreshed on the device), bytes uploaded by the last update, device bytes held by the value maps,
@@ -577,6 +578,33 @@ COSMO_HIP_API int32_t cosmo_hip_batch_apply_updates(cosmo_hip_batch* b);
 COSMO_HIP_API int32_t cosmo_hip_batch_update_qb(cosmo_hip_batch* b, int64_t count, const int64_t* members, const cosmo_hip_real* q, const cosmo_hip_real* bvec);
 COSMO_HIP_API int32_t cosmo_hip_batch_warm_restart(cosmo_hip_batch* b);
 COSMO_HIP_API int32_t cosmo_hip_batch_get_qb(cosmo_hip_batch* b, int64_t k, cosmo_hip_real* q /* n or NULL */, cosmo_hip_real* bvec /* m or NULL */);
+/* New VALUES for the stored entries of P and / or A of members of a finalised batch (the counterpart of cosmo_hip_update_matrices): same pattern, in the
+ * order of the P_nzval / A_nzval arrays cosmo_hip_batch_set_problem received for that member (NULL = unchanged).
+ * cosmo_hip_batch_stage_matrices: after set_params (INVALID before it, or for k out of range); stages the values of member k on the host.  apply_scaling
+ *   = 0: taken as given (the caller scaled them, as for set_problem); 1: the batch's D, E, c are applied on the device, A_ij <- a * (E_i * D_j),
+ *   P_ij <- (p * (D_i * D_j)) * c.  Both parts of one member take the same apply_scaling within one update (INVALID otherwise).
+ * cosmo_hip_batch_apply_updates then sends the staged members in one host-to-device copy of their own ({member, flags, nnzP, nnzA, offset} per
+ *   member, then nnzP + nnzA values each) next to the q / b copy, and one launch (k_batch_update_matrices, one workgroup per staged member) scales the
+ *   values once and gathers them into every value array the batch holds for the member: the CSR copies of A and A', the rows of [P | A'], the
+ *   member's LDS image (any of its layouts; padding and index arrays untouched) and its row of the register-resident diagonal of P.  The index maps
+ *   were recorded by set_problem / set_params and are uploaded with the first staged update.  Pattern, cones, row classes, D, E, c, rho and the
+ *   iterates stay; no device array of the batch is reallocated and cosmo_hip_batch_kernel_info is unchanged.  A direct batch factorises the staged
+ *   members, and only those, again on the kept analysis with their current rho; a member whose factor fails the inertia check makes the call return
+ *   COSMO_HIP_ERR_INVALID ("Objective function is not convex. (member k)") -- the other members are valid, and a later valid update of that member
+ *   restores it.
+ * cosmo_hip_batch_update_matrices: stage `count` members and apply.  P_vals / A_vals: the members' value arrays one after the other (or NULL).
+ * cosmo_hip_batch_update_matrices_info: out = {updates applied, destination arrays refreshed per member and update, host rebuilds (always 0), bytes
+ *   uploaded by the last update, device bytes held by the maps, factorisations caused by updates, 0, 0}.
+ * cosmo_hip_batch_get_matrix_values: the device copy of member k's values, which = 0: CSR of A, 1: CSR of A' (the caller's CSC order of A), 2: rows of
+ *   [P | A'] (nnzP + nnzA values).
+ * cosmo_hip_batch_get_image: the raw bytes of member k's LDS image followed by its row of the register-resident diagonal of P (each only where the
+ *   batch has it); *bytes_out is their size, out (capacity bytes; NULL: size only) receives them.  Read-back for tests and diagnosis. */
+COSMO_HIP_API int32_t cosmo_hip_batch_stage_matrices(cosmo_hip_batch* b, int64_t k, const cosmo_hip_real* P_nzval, const cosmo_hip_real* A_nzval, int32_t apply_scaling);
+COSMO_HIP_API int32_t cosmo_hip_batch_update_matrices(cosmo_hip_batch* b, int64_t count, const int64_t* members, const cosmo_hip_real* P_vals,
+                                                      const cosmo_hip_real* A_vals, int32_t apply_scaling);
+COSMO_HIP_API int32_t cosmo_hip_batch_update_matrices_info(cosmo_hip_batch* b, int64_t out[8]);
+COSMO_HIP_API int32_t cosmo_hip_batch_get_matrix_values(cosmo_hip_batch* b, int64_t k, int32_t which, cosmo_hip_real* out);
+COSMO_HIP_API int32_t cosmo_hip_batch_get_image(cosmo_hip_batch* b, int64_t k, void* out, int64_t capacity, int64_t* bytes_out);
 /* Device Ruiz equilibration of a batch (csrc/batch_ruiz.hip): scale_ruiz! (src/scaling.jl:21-116) of every member in ONE launch, one workgroup per
  * member, no host round trip -- the rounds, rectify_set_scalings!, the Box bounds and the reciprocals.
  * cosmo_hip_batch_scale_ruiz: after every cosmo_hip_batch_set_problem and cosmo_hip_batch_set_cones, before cosmo_hip_batch_set_params and INSTEAD of
@@ -653,6 +681,10 @@ COSMO_HIP_API int32_t cosmo_hip_batch_group_get_accel_stats(cosmo_hip_batch_grou
  * class batch; reverse_scaling! + scale_variables! on the host and cosmo_hip_set_iterates for members on their own handles).  get_qb reads the scaled
  * vectors of a member of a class batch (UNSUPPORTED for a member on its own handle). */
 COSMO_HIP_API int32_t cosmo_hip_batch_group_stage_qb(cosmo_hip_batch_group* g, int64_t k, const cosmo_hip_real* q, const cosmo_hip_real* bvec);
+/* New values of P / A of problem k (see cosmo_hip_batch_stage_matrices): forwarded to the problem's class batch; a member on its own handle keeps the
+ * arrays until cosmo_hip_batch_group_apply_updates calls cosmo_hip_update_matrices on that handle. */
+COSMO_HIP_API int32_t cosmo_hip_batch_group_stage_matrices(cosmo_hip_batch_group* g, int64_t k, const cosmo_hip_real* P_nzval, const cosmo_hip_real* A_nzval,
+                                                           int32_t apply_scaling);
 COSMO_HIP_API int32_t cosmo_hip_batch_group_apply_updates(cosmo_hip_batch_group* g);
 COSMO_HIP_API int32_t cosmo_hip_batch_group_warm_restart(cosmo_hip_batch_group* g);
 COSMO_HIP_API int32_t cosmo_hip_batch_group_get_qb(cosmo_hip_batch_group* g, int64_t k, cosmo_hip_real* q, cosmo_hip_real* bvec);
