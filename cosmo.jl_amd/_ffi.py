@@ -83,6 +83,9 @@ SIGNATURES = {
     "cosmo_hip_set_accelerator": (C.c_int32, [C.c_void_p, C.POINTER(AccelParams)]),
     "cosmo_hip_get_accel_stats": (C.c_int32, [C.c_void_p, _PI64]),
     "cosmo_hip_get_accel_restarts": (C.c_int32, [C.c_void_p, _PI64]),
+    "cosmo_hip_accel_pre": (C.c_int32, [C.c_void_p, C.c_int64, _PR, _PR, _PI64, _PR, _PR, _PR]),
+    "cosmo_hip_accel_post": (C.c_int32, [C.c_void_p, _PR, _PR, _PI32, _PR]),
+    "cosmo_hip_accel_restart": (C.c_int32, [C.c_void_p]),
     "cosmo_hip_scale_ruiz": (C.c_int32, [C.c_void_p, C.c_int64, C.c_double, C.c_double, _PR, _PR, _PD]),
     "cosmo_hip_update_qb": (C.c_int32, [C.c_void_p, _PR, _PR]),
     "cosmo_hip_update_matrices": (C.c_int32, [C.c_void_p, _PR, _PR, C.c_int32]),
@@ -379,7 +382,7 @@ class Handle:
         rv = self._f(rho_vec, self.m, "rho_vec")
         self._chk(self.lib.cosmo_hip_update_rho(self._h, _dp(rv)))
 
-    def set_accelerator(self, kind=ACCEL_ANDERSON, mem=15, min_mem=3, safeguard=True, safeguard_tol=2.0, start_iter=2, start_accuracy=None):
+    def set_accelerator(self, kind=ACCEL_ANDERSON, mem=15, min_mem=3, safeguard=True, safeguard_tol=2.0, start_iter=2, start_accuracy=None, eta_max=None):
         """`_make_accelerator!` (src/setup.jl:10-16); kind ACCEL_EMPTY removes it."""
         ap = AccelParams()
         self.lib.cosmo_hip_default_accel_params(C.byref(ap))
@@ -387,7 +390,41 @@ class Handle:
         ap.safeguard_tol, ap.start_iter = float(safeguard_tol), int(start_iter)
         if start_accuracy is not None:
             ap.start_accuracy = float(start_accuracy)
+        if eta_max is not None:
+            ap.eta_max = float(eta_max)
         self._chk(self.lib.cosmo_hip_set_accelerator(self._h, C.byref(ap)))
+
+    # ---- the accelerator one step at a time (the functions the accelerated loop calls, on given vectors; they overwrite the iterates) ----
+    ACCEL_PRE_INFO = ("attempted", "success", "l", "j", "restarts", "fail_singular", "fail_eta", "active", "mem")
+
+    def accel_pre(self, it, g, x):
+        """acceleration_pre! at loop index `it` on g = w, x = w_prev (length n + m).  Returns (candidate, info): info holds the ACCEL_PRE_INFO
+        integers, nrm_f, eta_norm, eta (mem) and R (mem x mem: the triangular factor, or M = L'F of the normal-equations variants)."""
+        N = self.n + self.m
+        w = np.array(self._f(g, N, "g"), copy=True)
+        wp = self._f(x, N, "x")
+        out = np.zeros(9, dtype=np.int64)
+        scal = np.zeros(2, dtype=self.dtype)
+        eta = np.zeros(32, dtype=self.dtype); R = np.zeros(32 * 32, dtype=self.dtype)
+        self._chk(self.lib.cosmo_hip_accel_pre(self._h, int(it), _dp(w), _dp(wp), out.ctypes.data_as(_PI64), _dp(scal), _dp(eta), _dp(R)))
+        info = {k: int(v) for k, v in zip(self.ACCEL_PRE_INFO, out)}
+        mem = info["mem"]
+        info.update(nrm_f=scal[0], eta_norm=scal[1], eta=eta[:mem].copy(), R=R[:mem * mem].reshape(mem, mem).T.copy())
+        return w, info
+
+    def accel_post(self, w, w_prev):
+        """acceleration_post! on the vectors after the ADMM step: (w, w_prev, declined, nrm_f_acc); a declined candidate is reset."""
+        N = self.n + self.m
+        w = np.array(self._f(w, N, "w"), copy=True)
+        wp = np.array(self._f(w_prev, N, "w_prev"), copy=True)
+        dec = C.c_int32(0)
+        na = np.zeros(1, dtype=self.dtype)
+        self._chk(self.lib.cosmo_hip_accel_post(self._h, _dp(w), _dp(wp), C.byref(dec), _dp(na)))
+        return w, wp, int(dec.value), na[0]
+
+    def accel_restart(self):
+        """CA.restart! (what a rho adaption calls): empties the history."""
+        self._chk(self.lib.cosmo_hip_accel_restart(self._h))
 
     def accel_restarts(self):
         """(restarts because the memory was full, restarts because rho was adapted) of the last optimize"""

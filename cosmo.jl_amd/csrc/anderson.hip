@@ -69,6 +69,7 @@ struct AaState {
   bool active = false;
   long long num_accelerated = 0, num_restarts = 0, num_declined = 0, num_accepted = 0;
   long long num_rho_restarts = 0;     // CA.restart! calls because rho was adapted (src/solver.jl:272-275)
+  long long step_restarts = 0;        // memory restarts under the step hooks (cosmo_hip_accel_pre), kept apart from the solve's counters
 };
 
 namespace {
@@ -592,5 +593,90 @@ extern "C" int32_t cosmo_hip_get_accel_stats(cosmo_hip_handle* h, int64_t out[6]
   out[5] = h->safeguarding_iter;
   if (!S) return COSMO_HIP_OK;
   out[0] = S->num_accelerated; out[1] = S->num_accepted; out[2] = S->num_declined; out[3] = S->num_restarts; out[4] = S->active ? 1 : 0;
+  return COSMO_HIP_OK;
+}
+
+// ---- step hooks: ONE acceleration_pre! / acceleration_post! on given vectors, through the functions optimize_accelerated calls ------------------
+static int32_t aa_step_enter(cosmo_hip_handle* h, const char* who) {
+  if (!h) return COSMO_HIP_ERR_INVALID;
+  if (hipSetDevice(h->device) != hipSuccess) return cosmo_fail(h, COSMO_HIP_ERR_HIP, "hipSetDevice failed");
+  if (h->comm || h->row_shard) return cosmo_fail(h, COSMO_HIP_ERR_UNSUPPORTED, "%s: not available with a communicator or on a row-sharded handle", who);
+  if (!aa_of(h)) return cosmo_fail(h, COSMO_HIP_ERR_INVALID, "%s: set_accelerator first", who);
+  if (!h->have_iterates) return cosmo_fail(h, COSMO_HIP_ERR_INVALID, "%s: set_iterates first", who);
+  return COSMO_HIP_OK;
+}
+static int32_t aa_step_load(cosmo_hip_handle* h, const real* w, const real* w_prev) {
+  const size_t bytes = sizeof(real) * (size_t)aa_of(h)->N;
+  if (!bytes) return COSMO_HIP_OK;
+  HIPCHK(h, hipMemcpyAsync(h->w, w, bytes, hipMemcpyHostToDevice, h->stream));
+  HIPCHK(h, hipMemcpyAsync(h->w_prev, w_prev, bytes, hipMemcpyHostToDevice, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));      // host buffers are never retained after return
+  return COSMO_HIP_OK;
+}
+static int32_t aa_step_store(cosmo_hip_handle* h, real* w, real* w_prev) {
+  const size_t bytes = sizeof(real) * (size_t)aa_of(h)->N;
+  if (bytes && w) HIPCHK(h, hipMemcpyAsync(w, h->w, bytes, hipMemcpyDeviceToHost, h->stream));
+  if (bytes && w_prev) HIPCHK(h, hipMemcpyAsync(w_prev, h->w_prev, bytes, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  return COSMO_HIP_OK;
+}
+
+extern "C" int32_t cosmo_hip_accel_pre(cosmo_hip_handle* h, int64_t it, real* w, const real* w_prev, int64_t info[9], real* scal, real* eta, real* Rout) {
+  CHK(aa_step_enter(h, "accel_pre"));
+  AaState* S = aa_of(h);
+  if ((!w || !w_prev) && S->N > 0) return cosmo_fail(h, COSMO_HIP_ERR_INVALID, "accel_pre: w and w_prev are required");
+  CHK(aa_step_load(h, w, w_prev));
+  const bool was_init = S->init_phase;
+  const int iter_before = S->iter;
+  const long long solve_restarts = S->num_restarts;
+  bool attempted = false;
+  const int32_t rc = aa_enqueue_pre(h, it, &attempted);
+  S->step_restarts += S->num_restarts - solve_restarts;      // the counters of the solve stay as they were
+  S->num_restarts = solve_restarts;
+  CHK(rc);
+  int success = 0;
+  CHK(aa_fetch_flags(h, &success, nullptr));                 // synchronises
+  const AaFlags* F = S->flags_host;
+  if (info) {
+    info[0] = attempted ? 1 : 0;
+    info[1] = (attempted && success) ? 1 : 0;
+    info[2] = std::min(S->iter, S->mem);
+    info[3] = (!S->active || was_init) ? -1 : iter_before % S->mem;
+    info[4] = S->step_restarts;
+    info[5] = F->fail_singular;
+    info[6] = F->fail_eta;
+    info[7] = S->active ? 1 : 0;
+    info[8] = S->mem;
+  }
+  if (scal) { scal[0] = F->nrm_f; scal[1] = F->eta_norm; }
+  if (eta || Rout) {
+    std::vector<real> buf((size_t)AA_MAX_MEM * AA_MAX_MEM + AA_MAX_MEM);
+    HIPCHK(h, hipMemcpyAsync(buf.data(), reinterpret_cast<const char*>(S->flags) + offsetof(AaFlags, R), sizeof(real) * buf.size(), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    if (Rout) for (int c = 0; c < S->mem; ++c) for (int r = 0; r < S->mem; ++r) Rout[(size_t)c * S->mem + r] = buf[(size_t)c * AA_MAX_MEM + r];
+    if (eta) for (int k = 0; k < S->mem; ++k) eta[k] = buf[(size_t)AA_MAX_MEM * AA_MAX_MEM + k];
+  }
+  return aa_step_store(h, w, nullptr);
+}
+
+extern "C" int32_t cosmo_hip_accel_post(cosmo_hip_handle* h, real* w, real* w_prev, int32_t* declined_out, real* nrm_f_acc) {
+  CHK(aa_step_enter(h, "accel_post"));
+  AaState* S = aa_of(h);
+  if ((!w || !w_prev) && S->N > 0) return cosmo_fail(h, COSMO_HIP_ERR_INVALID, "accel_post: w and w_prev are required");
+  CHK(aa_step_load(h, w, w_prev));
+  int declined = 0;
+  CHK(aa_enqueue_guard(h));
+  CHK(aa_fetch_flags(h, nullptr, &declined));
+  if (declined) CHK(aa_enqueue_reset(h));
+  if (declined_out) *declined_out = declined;
+  if (nrm_f_acc) *nrm_f_acc = S->flags_host->nrm_f_acc;
+  return aa_step_store(h, w, w_prev);
+}
+
+extern "C" int32_t cosmo_hip_accel_restart(cosmo_hip_handle* h) {
+  CHK(aa_step_enter(h, "accel_restart"));
+  CHK(aa_restart(h));
+  aa_of(h)->step_restarts = 0;
+  HIPCHK(h, hipStreamSynchronize(h->stream));
   return COSMO_HIP_OK;
 }

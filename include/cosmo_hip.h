@@ -263,6 +263,26 @@ COSMO_HIP_API int32_t cosmo_hip_get_accel_stats(cosmo_hip_handle* h, int64_t out
 /* out = {restarts of the accelerator because its memory was full (RestartedMemory), restarts because rho was adapted (CA.restart!, src/solver.jl:272-275)}
  * of the last optimize; the second equals num_rho_adaptions in test/UnitTests/AccelerationTests/adaptive_rho_acc_restarts.jl:24 */
 COSMO_HIP_API int32_t cosmo_hip_get_accel_restarts(cosmo_hip_handle* h, int64_t out[2]);
+/* ---- the accelerator one step at a time (test hooks; ABI 1005) ----
+ * The three calls below run the functions the accelerated loop of cosmo_hip_optimize runs (acceleration_pre!, acceleration_post!, CA.restart!)
+ * on vectors of length n + m given by the caller.  After set_accelerator and set_iterates; they overwrite the iterates (set_iterates again before
+ * iterating or optimizing) and leave safeguarding_iter and the counters of cosmo_hip_get_accel_stats / _restarts alone.  Not with a communicator
+ * or on a row-sharded handle (COSMO_HIP_ERR_UNSUPPORTED); without an accelerator COSMO_HIP_ERR_INVALID.
+ *
+ * cosmo_hip_accel_pre: acceleration_pre! at loop index `it` with g = w and x = w_prev: check_activation!, CA.update!(g, x), CA.accelerate!(g).
+ * w returns the candidate (g itself, bit for bit, when the step was not attempted or did not succeed).
+ * info = {attempted, success, l = min(iter, mem) columns in the history, 0-based column j this update wrote (-1: the call only initialised the
+ *         history, or the accelerator is not active), memory restarts (RestartedMemory) under these hooks since set_accelerator / accel_restart,
+ *         fail_singular, fail_eta (failed least-squares steps since the history was last emptied), active, effective mem = min(mem, n + m)}
+ * scal = {||f|| of this update, ||eta||_2} (as left by the last attempted step), eta[mem], R[mem * mem] column-major: the triangular factor of the
+ * default variant, the matrix M = L' F of the normal-equations variants.  scal, eta and R may be NULL. */
+COSMO_HIP_API int32_t cosmo_hip_accel_pre(cosmo_hip_handle* h, int64_t it, cosmo_hip_real* w, const cosmo_hip_real* w_prev, int64_t info[9],
+                                          cosmo_hip_real* scal, cosmo_hip_real* eta, cosmo_hip_real* R);
+/* acceleration_post! of a successful step on the given vectors after the ADMM step: declined = ||w_prev - w|| > safeguard_tol * ||f||; a declined
+ * candidate is reset (w = w_prev = g of the last update), otherwise both come back unchanged.  declined and nrm_f_acc (||w_prev - w||) may be NULL. */
+COSMO_HIP_API int32_t cosmo_hip_accel_post(cosmo_hip_handle* h, cosmo_hip_real* w, cosmo_hip_real* w_prev, int32_t* declined, cosmo_hip_real* nrm_f_acc);
+/* CA.restart! (empty_history!), what the loop calls after a rho adaption. */
+COSMO_HIP_API int32_t cosmo_hip_accel_restart(cosmo_hip_handle* h);
 /* Replaces scale_ruiz! (src/scaling.jl:21-116) for callers that hand over the UNSCALED problem: call after
  * cosmo_hip_set_problem + cosmo_hip_set_cones (unscaled data and Box bounds) and before cosmo_hip_set_params.  Runs
  * `iterations` (settings.scaling) steps of the modified Ruiz equilibration on the device-resident P, A, q, b, rectifies the

@@ -3,7 +3,17 @@ safeguarding on the device against the oracle's restatement of the same algorith
 the reference tree, so PARITY IS UNPINNED for this path: what is checked is (a) device == oracle restatement (same status,
 iteration counts within one check interval, same solution), (b) the assertions the reference's own tests make on
 accelerated runs (test/UnitTests/AccelerationTests, and every status / objective golden, which the reference asserts under
-its default = accelerated settings)."""
+its default = accelerated settings).
+
+What these whole-solve tests cover: the ORDER of the accelerated loop (acceleration_pre! before admm_z!, the safeguarding step and its
+extra ADMM iteration after the solve), the rho updates and infeasibility checks DEFERRED to the next non-accelerated iteration, the restart
+after a rho adaption, the activation rules inside a run, and the counters of a solve (accelerated / accepted / declined / restarts,
+safeguarding_iter in Result.iter) -- an accelerated run is chaotic in its last bits, so they compare at the end of a solve and within wide
+tolerances, which a subtly wrong accelerator survives (the safeguard declines a bad candidate and ADMM converges anyway).  The ARITHMETIC
+of the accelerator -- the Gram-Schmidt / Gram-matrix update, the least-squares solve, the candidate, the singular / eta_max / min_mem /
+memory-restart branches, the safeguard's norm and reset, for every kind, at one to three workgroups and l up to 32 -- is checked one update
+and one candidate at a time against a long-double reference in tests/test_gpu_anderson_steps.py (this file's kernels, through
+Handle.accel_pre / accel_post / accel_restart) and tests/test_gpu_batch_anderson_steps.py (the batch kernels' copy)."""
 import math
 
 import numpy as np
