@@ -201,6 +201,7 @@ extern "C" int32_t cosmo_hip_create(cosmo_hip_handle** out, int32_t device_id) {
   cosmo_hip_handle* h = new cosmo_hip_handle();
   h->device = device_id;
   cosmo_hip_default_params(&h->prm);
+  if (const char* e = getenv("COSMO_HIP_STEP_PASSES")) h->step_passes = atoi(e) ? 1 : 0;
   if (hipSetDevice(device_id) != hipSuccess || hipStreamCreate(&h->stream) != hipSuccess) { delete h; return COSMO_HIP_ERR_HIP; }
   if (hipMalloc((void**)&h->ctl, sizeof(Ctl)) != hipSuccess || hipHostMalloc((void**)&h->ctl_host, sizeof(Ctl)) != hipSuccess ||
       hipMalloc((void**)&h->partials, sizeof(real) * COSMO_NSLOTS_TOTAL * COSMO_MAX_PARTIALS) != hipSuccess) {
@@ -845,7 +846,7 @@ extern "C" int32_t cosmo_hip_set_iterates(cosmo_hip_handle* h, const real* x0, c
 // count of the previous window + 2, fixed for a whole window: on BASELINE config 5 (bench window: iterations 11-50 in one call) the
 // count creeps from 188 to 196, the window stalled twice and 65 % of its Krylov launches were no-ops; behind the rho update of
 // iteration 40 the count drops to 115 -> 87 and the budget stayed at 200 (tools/speculation_waste.py).
-// Now the count of every solve comes back through a pinned ring (4-byte copy + event behind k_tail), and solve s takes
+// Now the count of every solve comes back through a pinned ring (stored by k_tail into the mapped ring, or a 4-byte copy; + an event behind k_tail), and solve s takes
 //     budget = max + (max - min) / 2 + max / 40 + 3   of the counts K_{s-L-3} .. K_{s-L},      L = 2 solves of lag,
 // after WAITING for the event of solve s - L (already complete unless the host is more than L iterations ahead), so that the budget is a
 // function of the iteration history alone -- all ranks of a sharded run take the same decisions.  While the lagged solves predate a
@@ -859,7 +860,12 @@ int32_t solve_budget(cosmo_hip_handle* h, int* budget_out) {
   used = false;
   if (h->fb_mode == 1 && !h->fb_k) {
     if (const char* e = getenv("COSMO_HIP_BUDGET_FEEDBACK")) { if (atoi(e) == 0) h->fb_mode = 0; }
-    if (h->fb_mode == 1 && hipHostMalloc((void**)&h->fb_k, sizeof(int) * cosmo_hip_handle::FB_RING) != hipSuccess) { (void)hipGetLastError(); h->fb_k = nullptr; h->fb_mode = 0; }
+    const bool direct = h->step_passes && !h->row_shard;       // k_tail stores the count itself: the ring is mapped and coherent
+    if (h->fb_mode == 1 && hipHostMalloc((void**)&h->fb_k, sizeof(int) * cosmo_hip_handle::FB_RING, direct ? hipHostMallocMapped | hipHostMallocCoherent : hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); h->fb_k = nullptr; h->fb_mode = 0; }
+    if (h->fb_k && direct) {
+      for (int i = 0; i < cosmo_hip_handle::FB_RING; ++i) h->fb_k[i] = 0;
+      HIPCHK(h, hipHostGetDevicePointer((void**)&h->fb_k_dev, h->fb_k, 0));
+    }
   }
   *budget_out = h->budget;
   if (h->fb_mode != 1 || h->profiling || h->exact_launches) return COSMO_HIP_OK;
@@ -882,12 +888,21 @@ int32_t solve_budget(cosmo_hip_handle* h, int* budget_out) {
   *budget_out = b;
   return COSMO_HIP_OK;
 }
+// Device address of the ring entry of the next solve to be recorded, where k_tail stores the Krylov count itself -- on every path, also the early
+// returns of a halted or stalled loop, so the entry holds what a copy of ctl->cg_k behind the tail would have fetched.  nullptr: no such store, and
+// feedback_record copies the count (COSMO_HIP_STEP_PASSES=0, row-sharded handles, MINRES routes).  A tail that no record follows (kkt_resume) fills
+// the entry of the NEXT recorded solve, whose own tail overwrites it before its event; the host reads recorded entries only.
+int* feedback_slot(const cosmo_hip_handle* h) {
+  if (h->fb_mode != 1 || !h->fb_k_dev || h->row_shard || h->route == KKT_MINRES_FULL || h->route == KKT_MINRES_REDUCED) return nullptr;
+  return h->fb_k_dev + h->fb_recorded % cosmo_hip_handle::FB_RING;
+}
+// Behind k_tail of a loop solve: the event solve_budget waits for, and (where the tail did not store it) the copy of the count
 int32_t feedback_record(cosmo_hip_handle* h) {
   if (h->fb_mode != 1 || !h->fb_k) return COSMO_HIP_OK;
   const int R = cosmo_hip_handle::FB_RING;
   const int slot = (int)(h->fb_recorded % R);
   if (!h->fb_ev[slot]) HIPCHK(h, hipEventCreateWithFlags(&h->fb_ev[slot], hipEventDisableTiming));
-  HIPCHK(h, hipMemcpyAsync(&h->fb_k[slot], &h->ctl->cg_k, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+  if (!feedback_slot(h)) HIPCHK(h, hipMemcpyAsync(&h->fb_k[slot], &h->ctl->cg_k, sizeof(int), hipMemcpyDeviceToHost, h->stream));
   HIPCHK(h, hipEventRecord(h->fb_ev[slot], h->stream));
   h->fb_recorded += 1;
   return COSMO_HIP_OK;

@@ -289,7 +289,10 @@ struct cosmo_hip_handle {
   // Krylov budget feedback (api.hip: solve_budget): Krylov count of every solve of the loop, copied back asynchronously
   static const int FB_RING = 64;
   int* fb_k = nullptr;                 // pinned ring, entry s % FB_RING = cg_k of loop solve s
-  hipEvent_t fb_ev[FB_RING] = {};      // recorded behind the copy of solve s
+  int* fb_k_dev = nullptr;             // device address of the ring where k_tail stores the count itself (step_passes; nullptr: copied behind k_tail)
+  int step_passes = 1;                 // COSMO_HIP_STEP_PASSES (cosmo_hip_create; 0: the sequence of before, same bits): k_tail in loop mode stores the
+                                       // Krylov count into the ring and keeps s_tl, which nothing reads, in registers; the PSD plan reads the same switch
+  hipEvent_t fb_ev[FB_RING] = {};      // recorded behind k_tail (behind the copy) of solve s
   long long fb_recorded = 0;           // loop solves recorded so far
   long long fb_from = 0;               // first solve whose count describes the CURRENT regime (start, rho change or stall)
   int fb_mode = 1;                     // COSMO_HIP_BUDGET_FEEDBACK=0: window maximum + 2 only
@@ -349,7 +352,8 @@ int32_t sync_ctl(cosmo_hip_handle* h);
 int32_t rebuild_cone_plans(cosmo_hip_handle* h);
 int32_t reclassify_after_scaling(cosmo_hip_handle* h);
 int32_t solve_budget(cosmo_hip_handle* h, int* budget_out);     // Krylov budget of the next loop solve
-int32_t feedback_record(cosmo_hip_handle* h);                   // its Krylov count, copied back behind the solve
+int32_t feedback_record(cosmo_hip_handle* h);                   // its Krylov count, stored by k_tail or copied back behind the solve
+int* feedback_slot(const cosmo_hip_handle* h);                  // ... where k_tail stores it (nullptr: copied)
 
 // CG operator split (api.hip); any_a: build the split for any A (row sharding), fold: assemble it where sparse enough (cg_fold.hip),
 // keeping the rows of A with >= factor_min nonzeros factored (0: none)

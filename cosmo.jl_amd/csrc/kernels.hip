@@ -415,15 +415,23 @@ __global__ __launch_bounds__(COSMO_BS) void k_cg_upd(Ctl* __restrict__ ctl, int 
 //   w_s = w_s + alpha (s_tl - s) ; w_x = w_x + alpha (x_tl - w_x)      (solver.jl:63-64)
 // loop_mode 1: also detects an exhausted Krylov budget (stall) and advances the device counters.
 // loop_mode 0: fine-grained solve (only nu is produced).
+// fb_slot (loop mode, nullable): entry of the host's pinned, mapped ring of Krylov counts (api.hip: feedback_slot).  It receives ctl->cg_k on EVERY path,
+// the early returns included: what a copy of ctl->cg_k behind this launch would fetch.
+// keep_s_tl 0 (loop mode): s_tl stays in registers -- nothing reads the buffer (the loop's other kernels, the getters of include/cosmo_hip.h and the
+// bindings do not; the MINRES tail writes its own) -- which saves 8 m bytes of stores per iteration.
 __global__ __launch_bounds__(COSMO_BS) void k_tail(Ctl* __restrict__ ctl, int loop_mode, CsrView A, long long n, long long m,
                                                    real alpha, const real* __restrict__ x_tl,
                                                    const real* __restrict__ ls_s, const real* __restrict__ rho,
                                                    const real* __restrict__ s, real* __restrict__ nu,
-                                                   real* __restrict__ s_tl, real* __restrict__ w, int nblk_rows) {
+                                                   real* __restrict__ s_tl, real* __restrict__ w, int nblk_rows,
+                                                   int* __restrict__ fb_slot, int keep_s_tl) {
   if (loop_mode) {
-    if (ctl->halt) return;
-    if (!ctl->cg_done) {
-      if (blockIdx.x == 0 && threadIdx.x == 0) { ctl->stalled = 1; ctl->halt = 1; }
+    const int halt = ctl->halt;
+    if (halt || !ctl->cg_done) {
+      if (blockIdx.x == 0 && threadIdx.x == 0) {
+        if (fb_slot) *fb_slot = ctl->cg_k;
+        if (!halt) { ctl->stalled = 1; ctl->halt = 1; }
+      }
       return;
     }
   }
@@ -440,7 +448,7 @@ __global__ __launch_bounds__(COSMO_BS) void k_tail(Ctl* __restrict__ ctl, int lo
           const real sv = s[row];
           const real wv = w[n + row];
           const real st = (R(2.0) * sv - wv) - nv / rh;
-          s_tl[row] = st;
+          if (keep_s_tl) s_tl[row] = st;
           w[n + row] = wv + alpha * (st - sv);
         }
       });
@@ -457,6 +465,7 @@ __global__ __launch_bounds__(COSMO_BS) void k_tail(Ctl* __restrict__ ctl, int lo
       ctl->solves += 1;
       ctl->kkt_iters_total += k;
       if (k > ctl->cg_k_max) ctl->cg_k_max = k;
+      if (fb_slot) *fb_slot = k;
     }
   }
 }
@@ -901,7 +910,8 @@ int32_t enqueue_tail(cosmo_hip_handle* h, int loop_mode) {
   const int gx = loop_mode ? ew_grid(h->n) : 0;
   prof_begin(h, KC_TAIL);
   hipLaunchKernelGGL(k_tail, dim3(gr + gx), dim3(COSMO_BS), 0, h->stream, h->ctl, loop_mode, view_of(h->A), h->n, h->m,
-                     h->prm.alpha, h->x_tl, h->ls_s, h->rho, h->s, h->nu, h->s_tl, h->w, gr);
+                     h->prm.alpha, h->x_tl, h->ls_s, h->rho, h->s, h->nu, h->s_tl, h->w, gr, loop_mode ? feedback_slot(h) : (int*)nullptr,
+                     (loop_mode && h->step_passes) ? 0 : 1);
   prof_end(h);
   h->spmv_calls[0] += 1;
   HIPCHK(h, hipGetLastError());

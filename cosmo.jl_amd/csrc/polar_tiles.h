@@ -65,6 +65,19 @@ struct PolarBatchPlan {
 // nullptr, or the reason why the batch cannot be planned (out is then incomplete)
 const char* polar_plan_batch(const std::vector<PolarBatchIn>& in, const PolarTileOpts& o, PolarBatchPlan& out);
 
+// ---- cone-local workgroup ids of the batch's populate-type kernels ---------------------------------------------------------------------------------
+// The bpx workgroups of a cone share id % 8, i.e. (round-robin dispatch) one XCD and its L2: id = 8 * ((cone / 8) * bpx + bx) + cone % 8 on a 1-D grid of
+// 8 * bpx * ceil(n / 8) workgroups; the ids of a short last group of cones decode to "none".  Placement is a matter of speed only.  constexpr: the
+// kernels decode with the same code that tests/test_polar_passes_host.py checks on the CPU.
+struct PolarWg { int cone, bx; };   // cone == -1: none
+constexpr int polar_wg_grid(int n, int bpx) { return kPolarXcds * bpx * ((n + kPolarXcds - 1) / kPolarXcds); }
+constexpr int polar_wg_id(int cone, int bx, int bpx) { return kPolarXcds * ((cone / kPolarXcds) * bpx + bx) + cone % kPolarXcds; }
+constexpr PolarWg polar_wg_decode(int id, int n, int bpx) {
+  const int xcd = id & (kPolarXcds - 1), slot = id / kPolarXcds;
+  const int cone = kPolarXcds * (slot / bpx) + xcd;
+  return (id < 0 || cone >= n) ? PolarWg{-1, 0} : PolarWg{cone, slot % bpx};
+}
+
 // modelled cost of a ragged tile of a cone of side d: k-panels x slots of its fullest wave, in units of a tenth of a slot, + a fixed part for prologue
 // and epilogue
 long long polar_tile_cost(int d, int ext);

@@ -21,7 +21,10 @@
 // 8 d eps ||X||_F (1/8 of the parity tolerance 64 d eps), FALLBACK rounds (3 more lifting steps + the finishing steps, verified
 // again) run.  Two ways to schedule them (PolarPlan::speculate): ON DEMAND (default for a plan with at most two large cones, and for
 // the batch) -- after the main schedule the host reads the verification flag, ONE small stream synchronisation per large cone / per
-// batch and projection, and enqueues a round only if it is needed, so the loop is NOT sync-free while such cones are present; or
+// batch and projection, and enqueues a round only if it is needed, so the loop is NOT sync-free while such cones are present (the batch, by default:
+// no copy -- k_bpolar_decide stores the flag into a mapped host word, the host waits for an EVENT behind it, and finish / rank are already enqueued behind
+// that event, gated on the device by the same flag, so they run while the host wakes up; only a failed verification takes the copy and the
+// synchronisation of before, with finish / rank enqueued again behind the repair rounds: PolarPlan::step_passes); or
 // SPECULATIVELY (default from three large cones on, COSMO_HIP_POLAR_SPECULATE=1 forces it) -- both rounds are always enqueued behind
 // a device-side gate, 26 no-op launches per cone and round, and a projection involves no host synchronisation at all (a problem with
 // many d > 256 cones would otherwise drain the pipeline once per cone in every iteration).  Eigenvalues so small that they never lift (|lambda| below
@@ -126,6 +129,14 @@ struct PolarPlan {
                              // (no host synchronisation inside a projection, 52 no-op launches).  Measured: cfg4 127.9 -> 129.0, cfg5 155.1 -> 157.7 it/s
                              // without speculation (profiles/r02_fallback_speculation.txt)
   int* gate_host = nullptr;  // pinned copy of PolarDev::gate for the non-speculative mode
+  // COSMO_HIP_STEP_PASSES (default 1; 0: the kernels and the sequence of before, same binary, same bits; profiles/step_passes.txt).  The passes around
+  // the batch's main schedule: k_bpolar_norm + k_bpolar_populate2 on cone-local workgroup ids instead of populate + scale, the persistent launch's
+  // counters cleared by populate2 instead of a memset kernel, and the on-demand verification decision of round 0 read from gate_map behind an event,
+  // with the gated finish / rank already enqueued (polar_enqueue_project_batch)
+  int step_passes = 1;
+  int* gate_map = nullptr;       // pinned, mapped, coherent host word written by k_bpolar_decide; gate_map_dev: its device address
+  int* gate_map_dev = nullptr;
+  hipEvent_t gate_ev = nullptr;  // recorded behind k_bpolar_decide of round 0
   int batch_wave = 0;        // COSMO_HIP_POLAR_BATCH_WAVE=1: wave-per-tile product kernel (k_symm_gemm_batch_w) for the 64 x 64 tile class.  Bit-identical
                              // to the workgroup-per-tile kernel; measured on BASELINE config 5: 50.7 vs 47.3 us per product, 150.2 vs 154.7 it/s => opt-in
   int batch_ragged = 1;      // block-balanced ragged tiles (k_symm_gemm_batch_r); COSMO_HIP_POLAR_BATCH_RAGGED=0: the 64 x 64 quadrant kernel
@@ -1546,9 +1557,61 @@ __global__ __launch_bounds__(COSMO_BS) void k_bpolar_scale(const Ctl* __restrict
   real* U = W + cn.woff + (ubuf ? ubuf[blockIdx.y] : 1) * n2;       // the buffer that is `iu` at the step where this cone joins the schedule
   for (long long i = (long long)blockIdx.x * COSMO_BS + threadIdx.x; i < n2; i += (long long)gridDim.x * COSMO_BS) U[i] = X[i] * inv;
 }
-__global__ __launch_bounds__(COSMO_BS) void k_bpolar_finish(const Ctl* __restrict__ ctl, int guard, const BatchCone* __restrict__ cones,
+// PolarPlan::step_passes: populate + scale as a norm pass that stores nothing but the partials, and one pass that writes X and U.  1-D grid with
+// cone-local workgroup ids (polar_wg_decode: the BPX workgroups of a cone on one XCD, so the strided half of polar_read's accesses and the second read of
+// the slice hit that XCD's L2); thread (bx, threadIdx.x) of a cone runs the loops and the additions of k_bpolar_populate.
+__global__ __launch_bounds__(COSMO_BS) void k_bpolar_norm(const Ctl* __restrict__ ctl, int guard, int n, const BatchCone* __restrict__ cones,
+                                                          const real* __restrict__ s, real* __restrict__ parts) {
+  if (guard && ctl->halt) return;
+  const PolarWg wg = polar_wg_decode((int)blockIdx.x, n, BPX);
+  if (wg.cone < 0) return;
+  __shared__ real red[COSMO_BS / 64];
+  const BatchCone cn = cones[wg.cone];
+  const real* x = s + cn.off;
+  const int d = cn.d;
+  real acc = 0.0;
+  for (int j = wg.bx; j < d; j += BPX) {
+    for (int i = threadIdx.x; i < d; i += COSMO_BS) { const real v = polar_read(x, cn.kind, d, i, j); acc += v * v; }
+  }
+  acc = block_sum(acc, red);
+  if (threadIdx.x == 0) parts[(size_t)wg.cone * 2 * BPX + wg.bx] = acc;
+}
+// X = the cone's matrix, U = X * (2 / ||X||_F) into buffer ubuf ? ubuf[cone] : 1: the sum of the partials, inv and the product are k_bpolar_scale's.
+// Workgroup 0 also clears the nsync words of the persistent launch's counters (sync != nullptr: the launch follows behind a kernel boundary and nothing
+// in between reads them), which saves the memset kernel in front of that launch.
+__global__ __launch_bounds__(COSMO_BS) void k_bpolar_populate2(const Ctl* __restrict__ ctl, int guard, int n, const BatchCone* __restrict__ cones,
+                                                               const real* __restrict__ s, const real* __restrict__ parts, real* __restrict__ W,
+                                                               real* __restrict__ bnrm, const int* __restrict__ ubuf, unsigned* __restrict__ sync, int nsync) {
+  if (guard && ctl->halt) return;
+  if (sync && blockIdx.x == 0) for (int k = threadIdx.x; k < nsync; k += COSMO_BS) sync[k] = 0u;
+  const PolarWg wg = polar_wg_decode((int)blockIdx.x, n, BPX);
+  if (wg.cone < 0) return;
+  const BatchCone cn = cones[wg.cone];
+  real nf2 = 0.0;
+  for (int k = 0; k < BPX; ++k) nf2 += parts[(size_t)wg.cone * 2 * BPX + k];       // same order in every thread: deterministic
+  const real nf = sqrt(nf2);
+  const real inv = (nf > R(0.0)) ? R(2.0) / nf : R(0.0);
+  if (wg.bx == 0 && threadIdx.x == 0) bnrm[wg.cone] = nf;
+  const real* x = s + cn.off;
+  const int d = cn.d, ld = cn.ld;
+  real* X = W + cn.woff;
+  real* U = X + (ubuf ? ubuf[wg.cone] : 1) * (long long)ld * ld;
+  for (int j = wg.bx; j < ld; j += BPX) {
+    for (int i = threadIdx.x; i < ld; i += COSMO_BS) {
+      real v = 0.0;
+      if (i < d && j < d) v = polar_read(x, cn.kind, d, i, j);
+      const long long o = (long long)j * ld + i;
+      X[o] = v;
+      U[o] = v * inv;
+    }
+  }
+}
+// skip_if (nullable): the launch is a no-op when *skip_if != 0 -- enqueued behind a verification whose result the host has not seen yet (PolarDev::gate)
+__global__ __launch_bounds__(COSMO_BS) void k_bpolar_finish(const Ctl* __restrict__ ctl, int guard, const int* __restrict__ skip_if,
+                                                            const BatchCone* __restrict__ cones,
                                                             real* __restrict__ W, int iu, real* __restrict__ s, real* __restrict__ parts) {
   if (guard && ctl->halt) return;
+  if (skip_if && *skip_if) return;
   __shared__ real red[COSMO_BS / 64];
   const BatchCone cn = cones[blockIdx.y];
   const long long n2 = (long long)cn.ld * cn.ld;
@@ -1570,9 +1633,10 @@ __global__ __launch_bounds__(COSMO_BS) void k_bpolar_finish(const Ctl* __restric
   tr = block_sum(tr, red);
   if (threadIdx.x == 0) parts[(size_t)blockIdx.y * 2 * BPX + BPX + blockIdx.x] = tr;
 }
-__global__ void k_bpolar_rank(const Ctl* __restrict__ ctl, int guard, int n, const BatchCone* __restrict__ cones, const real* __restrict__ parts,
-                              int* __restrict__ rank) {
+__global__ void k_bpolar_rank(const Ctl* __restrict__ ctl, int guard, const int* __restrict__ skip_if, int n, const BatchCone* __restrict__ cones,
+                              const real* __restrict__ parts, int* __restrict__ rank) {
   if (guard && ctl->halt) return;
+  if (skip_if && *skip_if) return;                      // as k_bpolar_finish
   const int c = blockIdx.x * blockDim.x + threadIdx.x;
   if (c >= n) return;
   real tr = 0.0;
@@ -1594,9 +1658,11 @@ __global__ __launch_bounds__(COSMO_BS) void k_bpolar_sumsq(const Ctl* __restrict
   acc = block_sum(acc, red);
   if (threadIdx.x == 0) vparts[(size_t)blockIdx.y * BPX + blockIdx.x] = acc;
 }
+// gate_map (nullable): device address of a pinned, coherent host word that receives every value this kernel gives pd->gate, so that the host learns the
+// decision from an event behind this launch instead of a copy
 __global__ __launch_bounds__(COSMO_BS) void k_bpolar_decide(const Ctl* __restrict__ ctl, int guard, PolarDev* __restrict__ pd, int* __restrict__ bgate, int round,
                                                             int last, int n, const BatchCone* __restrict__ cones, const real* __restrict__ vparts,
-                                                            const real* __restrict__ bnrm, real tol_factor) {
+                                                            const real* __restrict__ bnrm, real tol_factor, int* __restrict__ gate_map) {
   if (guard && ctl->halt) return;
   if (round > 0 && !pd->gate) return;
   __shared__ real red[COSMO_BS / 64];
@@ -1620,9 +1686,12 @@ __global__ __launch_bounds__(COSMO_BS) void k_bpolar_decide(const Ctl* __restric
   pd->err_last = emax;
   if (emax > pd->err_max || emax != emax) pd->err_max = emax;
   if (round == 0) pd->projections += 1; else pd->rounds += 1;
-  if (nfail == R(0.0)) { pd->verified += 1; pd->gate = 0; }
-  else if (last) { pd->unverified += 1; pd->gate = 0; }
-  else pd->gate = 1;
+  int g = 0;
+  if (nfail == R(0.0)) pd->verified += 1;
+  else if (last) pd->unverified += 1;
+  else g = 1;
+  pd->gate = g;
+  if (gate_map) *gate_map = g;
   (void)nchk;
 }
 
@@ -1635,6 +1704,8 @@ void polar_plan_destroy(cosmo_hip_handle* h) {
   if (q->parts) (void)hipFree(q->parts);
   if (q->nrm) (void)hipFree(q->nrm);
   if (q->gate_host) (void)hipHostFree(q->gate_host);
+  if (q->gate_map) (void)hipHostFree(q->gate_map);
+  if (q->gate_ev) (void)hipEventDestroy(q->gate_ev);
   if (q->sk_scratch) (void)hipFree(q->sk_scratch);
   if (q->sk_sync) (void)hipFree(q->sk_sync);
   if (q->d_bcones) (void)hipFree(q->d_bcones);
@@ -1669,6 +1740,7 @@ struct PolarKnobs {
   int streamk = 0, ts = 0, sk = 0;
   long long skg = 0;
   int ts96 = 0, wave = 0, flat = 0, ragged = 1, paired = -1, sort = 1, dataflow = -1, dataflow_grid = -1, occ = -1;
+  int step_passes = 1;
 };
 
 static PolarKnobs polar_read_knobs() {
@@ -1696,6 +1768,7 @@ static PolarKnobs polar_read_knobs() {
   k.paired = within("COSMO_HIP_POLAR_PAIRED", 0, 3, k.paired);                                              // form of the persistent launch's queue items (PolarPlan::df_pair)
   k.dataflow = flag("COSMO_HIP_POLAR_DATAFLOW", k.dataflow);                                                // persistent dependency-driven main schedule of the batch (default: by the batch's size)
   k.dataflow_grid = within("COSMO_HIP_POLAR_DATAFLOW_GRID", 8, 8192, k.dataflow_grid);                      // ... its workgroups (default: four per CU)
+  k.step_passes = flag("COSMO_HIP_STEP_PASSES", k.step_passes);                                             // 0: populate + scale, memset and verification copy of before (PolarPlan::step_passes)
   return k;
 }
 
@@ -1754,6 +1827,13 @@ int32_t polar_plan_create(cosmo_hip_handle* h) {
   o.streamk = k.streamk; o.ts = k.ts; o.sk = k.sk; o.skg = k.skg;
   HIPCHK(h, hipHostMalloc((void**)&q->gate_host, 8 * sizeof(int), hipHostMallocDefault));     // {gate, rounds, verified, unverified, projections} of PolarDev
   for (int i = 0; i < 8; ++i) q->gate_host[i] = 0;
+  q->step_passes = k.step_passes;
+  if (q->step_passes) {
+    HIPCHK(h, hipHostMalloc((void**)&q->gate_map, 16 * sizeof(int), hipHostMallocMapped | hipHostMallocCoherent));
+    for (int i = 0; i < 16; ++i) q->gate_map[i] = 0;
+    HIPCHK(h, hipHostGetDevicePointer((void**)&q->gate_map_dev, q->gate_map, 0));
+    HIPCHK(h, hipEventCreateWithFlags(&q->gate_ev, hipEventDisableTiming));
+  }
   HIPCHK(h, hipMalloc((void**)&q->dev, sizeof(PolarDev)));
   HIPCHK(h, hipMemset(q->dev, 0, sizeof(PolarDev)));
   memset(&q->seen, 0, sizeof(PolarDev));
@@ -1906,13 +1986,21 @@ int32_t polar_enqueue_project_batch(cosmo_hip_handle* h, real* s, int guard) {
       q->lgate_kmax = kmax;
     }
   }
-  hipLaunchKernelGGL(k_bpolar_populate, dim3(BPX, n), dim3(COSMO_BS), 0, st, h->ctl, guard, q->d_bcones, s, q->BW, q->bparts);
-  hipLaunchKernelGGL(k_bpolar_scale, dim3(BPX, n), dim3(COSMO_BS), 0, st, h->ctl, guard, q->d_bcones, q->bparts, q->BW, q->bnrm, adapt ? (const int*)q->d_ubuf : (const int*)nullptr);
-  int iu = 1, iy = 2, products = 0;
   // main schedule as ONE persistent dependency-driven launch (k_polar_dataflow): the products are collected instead of launched; the repair rounds
   // (rare) keep the launch-per-product form
   DfArgs dfa;
   bool df = q->dataflow && q->batch_ragged && q->nrtiles > 0 && !adapt && !h->profiling && 3 * (kmax + POLAR_NFIN) + 2 <= DF_MAX_PROD;
+  const bool df_cleared = df && q->step_passes;            // k_bpolar_populate2 clears the launch's counters: no memset kernel in front of the launch
+  if (q->step_passes) {
+    const int grid = polar_wg_grid(n, BPX);
+    hipLaunchKernelGGL(k_bpolar_norm, dim3(grid), dim3(COSMO_BS), 0, st, h->ctl, guard, n, q->d_bcones, s, q->bparts);
+    hipLaunchKernelGGL(k_bpolar_populate2, dim3(grid), dim3(COSMO_BS), 0, st, h->ctl, guard, n, q->d_bcones, s, q->bparts, q->BW, q->bnrm,
+                       adapt ? (const int*)q->d_ubuf : (const int*)nullptr, df_cleared ? q->d_df_sync : (unsigned*)nullptr, DF_SYNC_DONE + n);
+  } else {
+    hipLaunchKernelGGL(k_bpolar_populate, dim3(BPX, n), dim3(COSMO_BS), 0, st, h->ctl, guard, q->d_bcones, s, q->BW, q->bparts);
+    hipLaunchKernelGGL(k_bpolar_scale, dim3(BPX, n), dim3(COSMO_BS), 0, st, h->ctl, guard, q->d_bcones, q->bparts, q->BW, q->bnrm, adapt ? (const int*)q->d_ubuf : (const int*)nullptr);
+  }
+  int iu = 1, iy = 2, products = 0;
   dfa.nprod = 0;
   auto product = [&](int epi, const int* gate, int ia, int ib, int icin, int ic, real alpha, real beta) {
     if (df) { DfProd& pr = dfa.prod[dfa.nprod++]; pr.ia = ia; pr.ib = ib; pr.icin = icin; pr.ic = ic; pr.epi = epi; pr.pad = 0; pr.alpha = alpha; pr.beta = beta; return; }
@@ -1922,7 +2010,7 @@ int32_t polar_enqueue_project_batch(cosmo_hip_handle* h, real* s, int guard) {
   auto flush_dataflow = [&]() -> int32_t {
     if (!df) return COSMO_HIP_OK;
     for (int x = 0; x < 9; ++x) dfa.xoff[x] = q->df_xoff[x];
-    HIPCHK(h, hipMemsetAsync(q->d_df_sync, 0, sizeof(unsigned) * (DF_SYNC_DONE + q->bcones.size()), st));
+    if (!df_cleared) HIPCHK(h, hipMemsetAsync(q->d_df_sync, 0, sizeof(unsigned) * (DF_SYNC_DONE + q->bcones.size()), st));
     // HIP events around the launch (two records per projection): the bench's roofline takes the launch duration from them (cosmo_hip_polar_dataflow_stats)
     if (!q->df_ev[0]) { HIPCHK(h, hipEventCreate(&q->df_ev[0])); HIPCHK(h, hipEventCreate(&q->df_ev[1])); }
     if (q->df_ev_pending && hipEventQuery(q->df_ev[1]) == hipSuccess) {
@@ -1957,7 +2045,7 @@ int32_t polar_enqueue_project_batch(cosmo_hip_handle* h, real* s, int guard) {
     CHK(flush_dataflow());
     hipLaunchKernelGGL(k_bpolar_sumsq, dim3(BPX, n), dim3(COSMO_BS), 0, st, h->ctl, guard, gate, q->d_bcones, q->BW, iy, vparts);
     hipLaunchKernelGGL(k_bpolar_decide, dim3(1), dim3(COSMO_BS), 0, st, h->ctl, guard, q->dev, q->bgate, round, round == q->max_rounds ? 1 : 0, n, q->d_bcones,
-                       vparts, q->bnrm, q->tol_factor);
+                       vparts, q->bnrm, q->tol_factor, q->gate_map_dev);
     products += 2; q->launches[3] += 2;
     return COSMO_HIP_OK;
   };
@@ -1968,7 +2056,20 @@ int32_t polar_enqueue_project_batch(cosmo_hip_handle* h, real* s, int guard) {
   { double wsum = 0.0, w3 = 0.0;                             // what the launches cost: products of a cone weighted by its d^3
     for (int c = 0; c < n; ++c) { const double d3 = (double)q->bcones[c].d * q->bcones[c].d * q->bcones[c].d; w3 += d3; wsum += d3 * (3.0 * ((adapt ? q->bdepth[c].k : kmax) + POLAR_NFIN) + 2.0); }
     q->wprod_last = w3 > 0.0 ? wsum / w3 : 0.0; }
-  for (int r = 1; r <= q->max_rounds; ++r) {                 // guarded fallback rounds (even number of steps: iu is preserved)
+  // On-demand verification without a copy (step_passes; not with the adaptive depth, which needs the per-cone results, nor on a profiling handle): the
+  // decision of round 0 arrives in gate_map behind an event, and finish / rank are enqueued BEFORE the host waits for it, gated by PolarDev::gate on
+  // the device -- they read X, buffer 3 and buffer iu, the operands of the ungated finish when no repair ran.  Gate 0 (the rule): the projection is
+  // complete and finish runs while the host wakes up.  Gate 1: the two launches were no-ops and the rounds below run as before, copy included.  In a
+  // halted loop the word is stale, as a copy of the stale PolarDev::gate would be; every kernel is then a no-op either way.
+  bool finished = false;
+  if (q->step_passes && !adapt && !q->speculate && !h->profiling && q->max_rounds >= 1) {
+    HIPCHK(h, hipEventRecord(q->gate_ev, st));
+    hipLaunchKernelGGL(k_bpolar_finish, dim3(BPX, n), dim3(COSMO_BS), 0, st, h->ctl, guard, (const int*)&q->dev->gate, q->d_bcones, q->BW, iu, s, q->bparts);
+    hipLaunchKernelGGL(k_bpolar_rank, dim3((n + 63) / 64), dim3(64), 0, st, h->ctl, guard, (const int*)&q->dev->gate, n, q->d_bcones, q->bparts, p->rank);
+    HIPCHK(h, hipEventSynchronize(q->gate_ev));
+    finished = *(volatile int*)q->gate_map == 0;
+  }
+  for (int r = 1; r <= q->max_rounds && !finished; ++r) {    // guarded fallback rounds (even number of steps: iu is preserved)
     if (!q->speculate) {                                     // ask the device whether the last verification failed (and, round 1 of an adaptive run, which cones)
       HIPCHK(h, hipMemcpyAsync(q->gate_host, &q->dev->gate, (adapt && r == 1 ? 5 : 1) * sizeof(int), hipMemcpyDeviceToHost, st));
       if (r == 1 && q->bgate_host) HIPCHK(h, hipMemcpyAsync(q->bgate_host, q->bgate, sizeof(int) * (size_t)n, hipMemcpyDeviceToHost, st));   // per-cone results: depth control + compact repair list
@@ -2006,8 +2107,10 @@ int32_t polar_enqueue_project_batch(cosmo_hip_handle* h, real* s, int guard) {
     CHK(verify(r, q->bgate));
   }
   q->nrep = 0;
-  hipLaunchKernelGGL(k_bpolar_finish, dim3(BPX, n), dim3(COSMO_BS), 0, st, h->ctl, guard, q->d_bcones, q->BW, iu, s, q->bparts);
-  hipLaunchKernelGGL(k_bpolar_rank, dim3((n + 63) / 64), dim3(64), 0, st, h->ctl, guard, n, q->d_bcones, q->bparts, p->rank);
+  if (!finished) {
+    hipLaunchKernelGGL(k_bpolar_finish, dim3(BPX, n), dim3(COSMO_BS), 0, st, h->ctl, guard, (const int*)nullptr, q->d_bcones, q->BW, iu, s, q->bparts);
+    hipLaunchKernelGGL(k_bpolar_rank, dim3((n + 63) / 64), dim3(64), 0, st, h->ctl, guard, (const int*)nullptr, n, q->d_bcones, q->bparts, p->rank);
+  }
   HIPCHK(h, hipGetLastError());
   return COSMO_HIP_OK;
 }
