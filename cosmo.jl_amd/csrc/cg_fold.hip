@@ -133,38 +133,57 @@ __device__ __forceinline__ void cg_dirM_body(Ctl* __restrict__ ctl, int guard, i
   // partial assembly (FoldPlan::nd > 0): a column cc >= n of the stored matrix [Ms | Ad' rho_d] gathers the record tt[cc - n] = {(Ad r)_kd, (Ad u_prev)_kd}; the
   // rebuilt value x + beta y is then (Ad u_k)_kd, just as {r, u} gives u_k for the columns < n.  nd == 0: every column is < n and REC is ru[cc].
 #define REC(cc) (((cc) < (int)n) ? ru[(cc)] : tt[(cc) - (int)n])
+  // every argument the head needs: one group of s_load, one wait (device_utils.h: pin_args)
+  pin_args(ctl, guard, check_first, k, n, maxiter, part_rr, n_rr, M.rb, M.nb, M.xcd_affine, M.rowptr, M.col, M.val, ru, c, u, part_uc, pcol, pval, tt, tcur, nd);
+  if constexpr (PC) pin_args(part_rz);
+  if constexpr (PSM >= 1) pin_args(tpos);
+  if constexpr (PSM == 2) pin_args(srec, sovf, ad_c);
   if (check_first) { if (guard && ctl->halt) return; if (ctl->cg_done) return; }   // expected no-op (see k_cg_dirA): flags before any request
-  const real pa = partials_prefetch_sum(part_rr, n_rr);
-  real pz = 0.0;
-  if constexpr (PC) pz = partials_prefetch_sum(part_rz, n_rr);
+  // FIRST BATCH: everything whose address the arguments and the block index give -- the r'r partials, the tile descriptor, (col, val) of the tile-major
+  // padded copy, this thread's own {r, u} record and tile-major position, the control block.  HEAD_ISSUED() stands behind the last of these loads, the
+  // additions of the partials and the pins (the one wait) behind it.
+  // Tile-major padded copy (pcol != null; cap = SL * 256 slots per tile): the addresses depend on the block index only, so (col, val) travel with the
+  // descriptor and the partials -- the dependent chain is col -> gather, one memory round trip shorter (the working set comes back through the fabric at
+  // every kernel boundary: profiles/r04_cfg5_pmc_traffic.json).  Padding slots hold column 0 / value 0 and are masked by cnt0 once the descriptor has
+  // arrived.  Without the copy the same loads read element 0 of the CSR arrays and are not used (no branch in the head either way).
+  real pv[COSMO_PARTS_PER_THREAD], pvz[COSMO_PARTS_PER_THREAD];
+  partials_request(part_rr, n_rr, pv);
+  if constexpr (PC) partials_request(part_rz, n_rr, pvz);
   const int first_tile = tile_of_block(blockIdx.x, M.nb, M.xcd_affine);
   const bool have_tile = first_tile < M.nb;
-  int4 d = make_int4(0, 0, 0, 0);
-  if (have_tile) d = reinterpret_cast<const int4*>(M.rb)[first_tile];
+  const int4 d = reinterpret_cast<const int4*>(M.rb)[have_tile ? first_tile : 0];      // (masked by have_tile in `fast`; M.nb >= 1)
+  const bool tm = pcol != nullptr;
+  const int* __restrict__ col1 = tm ? pcol : M.col;
+  const real* __restrict__ val1 = tm ? pval : M.val;
   real av[SL]; real2 gv[SL];
-  int cnt0;
-  bool fast;
-  if (pcol) {
-    // tile-major padded copy (cap = SL * 256 slots per tile): the addresses depend on the block index only, so (col, val) are requested together
-    // with the descriptor and the partials -- the dependent chain is col -> gather, one memory round trip shorter (the working set comes back
-    // through the fabric at every kernel boundary: profiles/r04_cfg5_pmc_traffic.json).  Padding slots hold column 0 / value 0 and are masked by
-    // cnt0 once the descriptor has arrived.
-    int ccs[SL];
+  int ccs[SL];
 #pragma unroll
-    for (int it = 0; it < SL; ++it) {
-      const long long e = have_tile ? (long long)first_tile * (SL * COSMO_BS) + it * COSMO_BS + threadIdx.x : 0;
-      ccs[it] = pcol[e];
-      av[it] = pval[e];
-    }
+  for (int it = 0; it < SL; ++it) {
+    const long long e = (tm && have_tile) ? (long long)first_tile * (SL * COSMO_BS) + it * COSMO_BS + threadIdx.x : 0;
+    ccs[it] = col1[e];
+    av[it] = val1[e];
+  }
+  const long long i0 = (long long)blockIdx.x * COSMO_BS + threadIdx.x;
+  const real2 own = ru[i0 < n ? i0 : 0];
+  int tp0 = 0;
+  if constexpr (PSM >= 1) tp0 = tpos[i0 < nd ? i0 : 0];
+  const CtlHead ch = ctl_head_load(ctl);
+  HEAD_ISSUED();
+  const real pa = partials_fold(pv, n_rr);
+  real pz = 0.0;
+  if constexpr (PC) pz = partials_fold(pvz, n_rr);
+#pragma unroll
+  for (int it = 0; it < SL; ++it) PIN_V2(ccs[it], av[it]);
+  PIN_V4(pa, pz, own.x, own.y); PIN_V1(tp0); asm volatile("" :: "s"(d.x), "s"(d.y), "s"(d.z), "s"(d.w)); ctl_head_pin(ch);
+  // SECOND BATCH: the gathers, the row pointers, the row's record and its slot record (addresses from the columns and the descriptor)
+  const int cnt0 = d.w - d.z;
+  const bool fast = have_tile && cnt0 <= SL * COSMO_BS;            // a single long row takes the generic chunked path below
+  if (tm) {
 #pragma unroll
     for (int it = 0; it < SL; ++it) gv[it] = REC(ccs[it]);
-    cnt0 = d.w - d.z;
-    fast = have_tile && cnt0 <= SL * COSMO_BS;
 #pragma unroll
     for (int it = 0; it < SL; ++it) if (!(fast && it * COSMO_BS + (int)threadIdx.x < cnt0)) av[it] = 0.0;
   } else {
-    cnt0 = d.w - d.z;
-    fast = have_tile && cnt0 <= SL * COSMO_BS;            // a single long row takes the generic chunked path below
 #pragma unroll
     for (int it = 0; it < SL; ++it) {
       const int kk = it * COSMO_BS + threadIdx.x;
@@ -181,19 +200,16 @@ __device__ __forceinline__ void cg_dirM_body(Ctl* __restrict__ ctl, int guard, i
   const int rr_ = rowok ? rfirst : 0;
   const int pa_ = M.rowptr[rr_], pb_ = M.rowptr[rr_ + 1];
   const real2 rw = ru[rr_];                                       // {r, u_{k-1}} of this thread's row: u_k of the row for u'c
-  const long long i0 = (long long)blockIdx.x * COSMO_BS + threadIdx.x;
-  const real2 own = ru[i0 < n ? i0 : 0];
   int4 sr0 = make_int4(-1, -1, 0, 0);
-  int tp0 = 0;
   if constexpr (PSM == 2) sr0 = srec[rr_];
-  if constexpr (PSM >= 1) tp0 = tpos[i0 < nd ? i0 : 0];
-  if (guard && ctl->halt) return;
-  if (ctl->cg_done) return;
+  // (the second batch is not pinned: the flags are here already, and its loads cannot move behind the barrier of the reduction below, under which they travel)
+  if (guard && ch.halt) return;
+  if (ch.cg_done) return;
   __shared__ real lds[COSMO_NNZ_PER_BLOCK];
   __shared__ real red[COSMO_BS / 64];
-  if (k < 0) k = ctl->cg_k;                      // device-side index (captured chain, k >= 1): written by the k_cg_upd in front, by nobody during this kernel
-  const real tol = ctl->tol;
-  const real prev = (k == 0) ? 1.0 : ctl->resv[(k - 1) & 1];
+  if (k < 0) k = ch.cg_k;                        // device-side index (captured chain, k >= 1): written by the k_cg_upd in front, by nobody during this kernel
+  const real tol = ch.tol;
+  const real prev = (k == 0) ? 1.0 : (((k - 1) & 1) ? ch.rv1 : ch.rv0);
   const real rr = block_sum(pa, red);
   const real res = sqrt(rr);
   const bool done = (k >= maxiter) || (res <= tol);
@@ -310,6 +326,7 @@ __global__ __launch_bounds__(COSMO_BS) void k_cg_updF0(Ctl* __restrict__ ctl, in
     real u0 = 0.0, c0 = 0.0, x0 = 0.0, r0 = 0.0;
     if (i0 < n) { u0 = u[i0]; c0 = c[i0]; x0 = x[i0]; r0 = ru_old[i0].x; }
     const real pa = partials_prefetch_sum(part_uc, n_uc);
+    PIN_V1(pa);                                            // keeps the loads above in front of the two returns (device_utils.h)
     if (guard && ctl->halt) return;
     if (ctl->cg_done) return;
     if (k < 0) k = ctl->cg_kd;
@@ -367,6 +384,7 @@ __global__ __launch_bounds__(COSMO_BS) void k_cg_updF0(Ctl* __restrict__ ctl, in
   const int pa_ = Ad.rowptr[rr_], pb_ = Ad.rowptr[rr_ + 1];
   const real tk_ = tcur[rr_];
   const real pa = partials_prefetch_sum(part_uc, n_uc);
+  PIN_V1(pa);                                              // keeps the loads above in front of the two returns (device_utils.h)
   if (guard && ctl->halt) return;
   if (ctl->cg_done) return;
   if (k < 0) k = ctl->cg_kd;
@@ -414,6 +432,9 @@ __global__ __launch_bounds__(COSMO_BS) void k_cg_updF(Ctl* __restrict__ ctl, int
                                                       const real* __restrict__ ad_rc, real* __restrict__ ad_rn) {
   __shared__ real lds[COSMO_NNZ_PER_BLOCK];
   __shared__ real red[COSMO_BS / 64];
+  // every argument either half needs: one group of s_load, one wait (device_utils.h: pin_args)
+  pin_args(ctl, guard, k, n, part_uc, n_uc, u, c, x, r, part_rr, ru_old, ru_new, gE, Ad.rb, Ad.nb, Ad.rowptr, Ad.col, Ad.val, Ad.split, tt, tcur, tpos, iav, lrp);
+  if constexpr (PSM == 2) pin_args(srec, sovf, ad_c, ad_rc, ad_rn); else pin_args(icol);
   if ((int)blockIdx.x < gE) {
     // ---- workgroups [0, gE): the vector update of k_cg_upd<false>, r_old taken from the old records ------------------------------------------------
     const long long i0 = (long long)blockIdx.x * COSMO_BS + threadIdx.x;
@@ -421,13 +442,17 @@ __global__ __launch_bounds__(COSMO_BS) void k_cg_updF(Ctl* __restrict__ ctl, int
     const real u0 = u[i0c], c0 = c[i0c], x0 = x[i0c], r0 = ru_old[i0c].x;
     int4 sr0 = make_int4(-1, -1, 0, 0);
     if constexpr (PSM == 2) sr0 = srec[i0c];
-    const real pa = partials_prefetch_sum(part_uc, n_uc);
-    const int halt = ctl->halt, cdone = ctl->cg_done, kd_ = ctl->cg_kd;
-    const real rv0 = ctl->resv[0], rv1 = ctl->resv[1];
-    if (guard && halt) return;
-    if (cdone) return;
-    if (k < 0) k = kd_;
-    const real res = (k & 1) ? rv1 : rv0;
+    real pv[COSMO_PARTS_PER_THREAD];
+    partials_request(part_uc, n_uc, pv);
+    const CtlHead ch = ctl_head_load(ctl);
+    HEAD_ISSUED();
+    // ONE batch: nothing above depends on anything but the arguments; the flags are decided on only behind the last load
+    const real pa = partials_fold(pv, n_uc);
+    PIN_V4(u0, c0, x0, r0); PIN_V4(sr0.x, sr0.y, sr0.z, sr0.w); PIN_V1(pa); ctl_head_pin(ch);
+    if (guard && ch.halt) return;
+    if (ch.cg_done) return;
+    if (k < 0) k = ch.cg_kd;
+    const real res = (k & 1) ? ch.rv1 : ch.rv0;
     const real uc = block_sum(pa, red);
     const real alpha = (res * res) / uc;
     real acc = 0.0;
@@ -480,13 +505,20 @@ __global__ __launch_bounds__(COSMO_BS) void k_cg_updF(Ctl* __restrict__ ctl, int
   }
   const int pa_ = lrp[ft * (COSMO_BS + 1) + threadIdx.x], pb_ = lrp[ft * (COSMO_BS + 1) + threadIdx.x + 1];
   const real tk_ = tcur[(long long)ft * COSMO_BS + threadIdx.x];
-  const real pa = partials_prefetch_sum(part_uc, n_uc);
-  const int halt = ctl->halt, cdone = ctl->cg_done, kd_ = ctl->cg_kd;
-  const real rv0 = ctl->resv[0], rv1 = ctl->resv[1];
-  if (guard && halt) return;
-  if (cdone) return;
-  if (k < 0) k = kd_;
-  const real res = (k & 1) ? rv1 : rv0;
+  real pv[COSMO_PARTS_PER_THREAD];
+  partials_request(part_uc, n_uc, pv);
+  const CtlHead ch = ctl_head_load(ctl);
+  HEAD_ISSUED();
+  const real pa = partials_fold(pv, n_uc);
+  if constexpr (PSM == 2) {                         // ONE batch (PSM == 1: the gathers are the second)
+#pragma unroll
+    for (int it = 0; it < ADSL; ++it) { PIN_V2(av[it], gr[it]); PIN_V1(gc[it]); }
+  }
+  PIN_V4(pa_, pb_, tk_, pa); asm volatile("" :: "s"(d.x), "s"(d.y), "s"(d.z), "s"(d.w)); ctl_head_pin(ch);
+  if (guard && ch.halt) return;
+  if (ch.cg_done) return;
+  if (k < 0) k = ch.cg_kd;
+  const real res = (k & 1) ? ch.rv1 : ch.rv0;
   const int cnt0 = d.w - d.z;
   const bool fast = have_tile && cnt0 <= ADSL * COSMO_BS;
   const int rfirst = d.x + threadIdx.x;
@@ -909,6 +941,7 @@ static bool fold_chain_ready(cosmo_hip_handle* h, FoldPlan* f) {
 int32_t fold_enqueue_iterations(cosmo_hip_handle* h, int guard, int k_begin, int count) {
   FoldPlan* f = (FoldPlan*)h->fold;
   const int gE = ew_grid(h->n);
+  if (f->M.grid < 1 || gE < 1) return COSMO_HIP_ERR_INVALID;       // the partial counts of the branch-free loads (device_utils.h: partials_request) are these grids
   int k = k_begin;
   const int k_end = k_begin + count;
   if (guard == 1 && k_begin == 0 && count > 1 && fold_chain_ready(h, f)) {

@@ -56,6 +56,7 @@ __global__ __launch_bounds__(COSMO_BS) void k_sr_update_A(Ctl* __restrict__ ctl,
                                                           const real* __restrict__ rho, real* __restrict__ tmp) {
   const real pg = partials_prefetch_sum(part_g_in, n_g);
   const real pd = partials_prefetch_sum(part_d, n_d);
+  PIN_V2(pg, pd);                                          // keeps the loads above in front of the two returns (device_utils.h)
   if (guard && ctl->halt) return;
   if (ctl->cg_done) return;
   __shared__ real lds[COSMO_NNZ_PER_BLOCK];
@@ -188,6 +189,7 @@ __global__ __launch_bounds__(COSMO_BS) void k_sr_M(Ctl* __restrict__ ctl, int gu
   const real2 own_rw = rec2[2 * (size_t)rr_];
   const real2 own_sp = rec2[2 * (size_t)rr_ + 1];
   const real own_x = x[rr_];
+  PIN_V2(pg, pd);                                          // keeps the loads above in front of the two returns (device_utils.h)
   if (guard && ctl->halt) return;
   if (ctl->cg_done) return;
   if (k < 0) k = ctl->sr_k[par];                 // device-side index (captured chain, k >= 1): written by the launch in front, by nobody during this one

@@ -37,6 +37,35 @@ __device__ __forceinline__ int tile_of_block(int b, int nb, int affine) {
   return (affine && b < (per << 3)) ? (b & 7) * per + (b >> 3) : b;
 }
 
+// Heads of the latency-bound Krylov kernels (profiles/krylov_heads.txt).  The compiler fetches kernel arguments and the words of the control block
+// LAZILY -- an s_load right in front of the first use, each behind its own s_waitcnt lgkmcnt(0) -- and sinks loads whose values an early `return` does
+// not need below that return: a head written as "request everything, then decide" comes out as a chain of serial trips.  An empty asm statement that
+// names a value makes it exist at that point, so its load is issued (and waited for) in front of it; values named by ONE statement are requested
+// together and waited for once.  No instruction is emitted and no expression changes.
+template <class T>
+__device__ __forceinline__ void pin_arg(T v) { asm volatile("" :: "s"(v)); }
+template <class... T>
+__device__ __forceinline__ void pin_args(T... v) { (pin_arg(v), ...); }        // wave-uniform values: kernel arguments
+#define PIN_V1(a) asm volatile("" :: "v"(a))
+#define PIN_V2(a, b) asm volatile("" :: "v"(a), "v"(b))
+#define PIN_V4(a, b, c, d) asm volatile("" :: "v"(a), "v"(b), "v"(c), "v"(d))
+
+// The scalars of the control block a Krylov kernel decides on, requested as ONE batch (next to the kernel's first batch of vector loads) and pinned by
+// ctl_head_pin behind the last of those loads.  A launch writes some of these words itself (workgroup 0: cg_done, cg_kd and resv[k & 1] in the direction
+// kernels, cg_k in the update kernels): such a word may arrive here in either state and is never USED by the kernel that writes it -- the direction
+// kernels use cg_k, tol and resv[(k - 1) & 1], the update kernels cg_kd and resv[k & 1]; cg_done is read as before (set early by workgroup 0, it ends a
+// workgroup that would have computed the same `done` itself).
+struct CtlHead { int halt, cg_done, cg_k, cg_kd; real rv0, rv1, tol; };
+__device__ __forceinline__ CtlHead ctl_head_load(const Ctl* __restrict__ ctl) {
+  CtlHead c;
+  c.halt = ctl->halt; c.cg_done = ctl->cg_done; c.cg_k = ctl->cg_k; c.cg_kd = ctl->cg_kd;
+  c.rv0 = ctl->resv[0]; c.rv1 = ctl->resv[1]; c.tol = ctl->tol;
+  return c;
+}
+__device__ __forceinline__ void ctl_head_pin(const CtlHead& c) {
+  asm volatile("" :: "s"(c.halt), "s"(c.cg_done), "s"(c.cg_k), "s"(c.cg_kd), "s"(c.rv0), "s"(c.rv1), "s"(c.tol));
+}
+
 // Butterfly reductions (xor 32, 16, 8, 4, 2, 1): every lane ends with the same value, combination order is fixed => deterministic.
 // No step goes through the LDS crossbar (ds_bpermute, what __shfl_xor compiles to): the steps across rows of 16 lanes use gfx950's
 // v_permlane32_swap / v_permlane16_swap (with both operands = v they leave {v[i], v[i ^ 32]} resp. {v[i], v[i ^ 16]} in the two result
@@ -136,21 +165,40 @@ __device__ __forceinline__ real block_max(real v, real* red) {
 // vmcnt(0), add per iteration -- up to eight serial L2 round trips at the head of every latency-bound Krylov kernel (k_cg_upd on
 // BASELINE config 2 reduces 2048 partials: 4 of its 5.3 us).  Missing slots contribute +0.0, which cannot change the sum: the running
 // sum starts at +0.0 and therefore is never -0.0.
+// The loads are BRANCH-FREE: a missing slot reads p[0] (always allocated; every count is the grid of the producing launch, hence >= 1) and
+// the +0.0 is selected afterwards.  Written as `(i < count) ? p[i] : 0.0` the load sits under a per-lane condition; the compiler then branches around
+// each of the eight loads and waits vmcnt(0) behind the first one -- a full drain of everything the caller had in flight, one whole trip at the head
+// of the kernel, with the other seven loads issued only after it (profiles/krylov_heads.txt; tests/test_isa_krylov_heads.py pins the count of drains).
+// The two halves are separate functions for the kernels that request more than the partials in their first batch: partials_request, the kernel's
+// other loads, HEAD_ISSUED(), partials_fold.  Without the scheduling barrier the compiler starts the additions as soon as the first partial can be
+// waited for and issues the rest of the batch BEHIND that (counted) wait -- one trip late.
 #define COSMO_PARTS_PER_THREAD (COSMO_MAX_PARTIALS / COSMO_BS)
-__device__ __forceinline__ real partials_prefetch_sum(const real* p, int count) {
-  real v[COSMO_PARTS_PER_THREAD];
+#define HEAD_ISSUED() __builtin_amdgcn_sched_barrier(0)
+__device__ __forceinline__ void partials_request(const real* p, int count, real (&v)[COSMO_PARTS_PER_THREAD]) {
 #pragma unroll
-  for (int k = 0; k < COSMO_PARTS_PER_THREAD; ++k) { const int i = (int)threadIdx.x + k * COSMO_BS; v[k] = (i < count) ? p[i] : R(0.0); }
+  for (int k = 0; k < COSMO_PARTS_PER_THREAD; ++k) { const int i = (int)threadIdx.x + k * COSMO_BS; v[k] = p[i < count ? i : 0]; }
+}
+__device__ __forceinline__ void partials_mask(real (&v)[COSMO_PARTS_PER_THREAD], int count) {
+#pragma unroll
+  for (int k = 0; k < COSMO_PARTS_PER_THREAD; ++k) { const int i = (int)threadIdx.x + k * COSMO_BS; v[k] = (i < count) ? v[k] : R(0.0); }
+}
+__device__ __forceinline__ real partials_fold(real (&v)[COSMO_PARTS_PER_THREAD], int count) {
+  partials_mask(v, count);
   real a = 0.0;
 #pragma unroll
   for (int k = 0; k < COSMO_PARTS_PER_THREAD; ++k) a += v[k];
   return a;
 }
+__device__ __forceinline__ void partials_load(const real* p, int count, real (&v)[COSMO_PARTS_PER_THREAD]) { partials_request(p, count, v); partials_mask(v, count); }
+__device__ __forceinline__ real partials_prefetch_sum(const real* p, int count) {
+  real v[COSMO_PARTS_PER_THREAD];
+  partials_request(p, count, v);
+  return partials_fold(v, count);
+}
 __device__ __forceinline__ real reduce_partials_sum(const real* p, int count, real* red) { return block_sum(partials_prefetch_sum(p, count), red); }
 __device__ __forceinline__ real reduce_partials_max(const real* p, int count, real* red) {
   real v[COSMO_PARTS_PER_THREAD];
-#pragma unroll
-  for (int k = 0; k < COSMO_PARTS_PER_THREAD; ++k) { const int i = (int)threadIdx.x + k * COSMO_BS; v[k] = (i < count) ? p[i] : R(0.0); }
+  partials_load(p, count, v);
   real a = 0.0;
 #pragma unroll
   for (int k = 0; k < COSMO_PARTS_PER_THREAD; ++k) { const real t = v[k]; a = (t > a || t != t) ? t : a; }   // a padding 0.0 never replaces a

@@ -242,13 +242,15 @@ __global__ __launch_bounds__(COSMO_BS) void k_cg_dir(Ctl* __restrict__ ctl, int 
   const long long i0 = (long long)blockIdx.x * COSMO_BS + threadIdx.x;
   real r0 = 0.0, u0 = 0.0;
   if (!check_only && i0 < n) { r0 = r[i0]; if (k != 0) u0 = u[i0]; }
-  const real pa = partials_prefetch_sum(part_rr, n_rr);      // in flight while the guards wait on their scalar loads
-  if (guard && ctl->halt) return;
-  if (ctl->cg_done) return;
+  const real pa = partials_prefetch_sum(part_rr, n_rr);
+  const CtlHead ch = ctl_head_load(ctl);                     // the control block travels with the operands and the partials: one wait (device_utils.h)
+  PIN_V2(r0, u0); PIN_V1(pa); ctl_head_pin(ch);
+  if (guard && ch.halt) return;
+  if (ch.cg_done) return;
   __shared__ real red[COSMO_BS / 64];
-  if (k < 0) k = ctl->cg_k;                      // device-side index (the check behind a captured chain, cg_fold.hip): nobody writes cg_k during this kernel
-  const real tol = ctl->tol;
-  const real prev = (k == 0) ? 1.0 : ctl->resv[(k - 1) & 1];
+  if (k < 0) k = ch.cg_k;                        // device-side index (the check behind a captured chain, cg_fold.hip): nobody writes cg_k during this kernel
+  const real tol = ch.tol;
+  const real prev = (k == 0) ? 1.0 : (((k - 1) & 1) ? ch.rv1 : ch.rv0);
   const real rr = block_sum(pa, red);
   const real res = sqrt(rr);
   const bool done = (k >= maxiter) || (res <= tol);
@@ -306,12 +308,17 @@ __global__ __launch_bounds__(COSMO_BS) void k_cg_dirA(Ctl* __restrict__ ctl, int
   const real rho_ = rho[rr_];
   const long long i0 = (long long)blockIdx.x * COSMO_BS + threadIdx.x;
   const real2 own = ru[i0 < n ? i0 : 0];
-  if (guard && ctl->halt) return;
-  if (ctl->cg_done) return;
+  // the control block's scalars as one batch of scalar loads (device_utils.h: CtlHead), decided on once the partials are here.  Only the partials are
+  // waited for; the statement also keeps every load above in front of the two returns (no load moves across it; with branch-free partial loads the
+  // compiler would otherwise sink them below the returns, behind the flags' trip)
+  const CtlHead ch = ctl_head_load(ctl);
+  PIN_V1(pa); ctl_head_pin(ch);
+  if (guard && ch.halt) return;
+  if (ch.cg_done) return;
   __shared__ real lds[COSMO_NNZ_PER_BLOCK];
   __shared__ real red[COSMO_BS / 64];
-  const real tol = ctl->tol;
-  const real prev = ctl->resv[(k - 1) & 1];
+  const real tol = ch.tol;
+  const real prev = ((k - 1) & 1) ? ch.rv1 : ch.rv0;
   const real rr = block_sum(pa, red);
   const real res = sqrt(rr);
   const bool done = (k >= maxiter) || (res <= tol);
@@ -360,15 +367,26 @@ __global__ __launch_bounds__(COSMO_BS) void k_cg_upd(Ctl* __restrict__ ctl, int 
                                                      real* __restrict__ x, real* __restrict__ r,
                                                      real* __restrict__ part_rr, real2* __restrict__ ru,
                                                      const real* __restrict__ dinv, real* __restrict__ part_rz) {
+  // ONE batch (device_utils.h: pin_args, CtlHead): the arguments; then the operands, the u'c partials and the control block, all behind one wait --
+  // absent elements read index 0 (n >= 1) and are never used
+  pin_args(ctl, guard, k, n, part_uc, n_uc, u, c, x, r, part_rr, ru);
+  if constexpr (PC) pin_args(dinv, part_rz);
   const long long i0 = (long long)blockIdx.x * COSMO_BS + threadIdx.x;
-  real u0 = 0.0, c0 = 0.0, x0 = 0.0, r0 = 0.0, d0 = 0.0;
-  if (i0 < n) { u0 = u[i0]; c0 = c[i0]; x0 = x[i0]; r0 = r[i0]; if constexpr (PC) d0 = dinv[i0]; }   // issued before the scalar work (latency overlap)
-  const real pa = partials_prefetch_sum(part_uc, n_uc);
-  if (guard && ctl->halt) return;
-  if (ctl->cg_done) return;
+  const long long i0c = i0 < n ? i0 : 0;
+  const real u0 = u[i0c], c0 = c[i0c], x0 = x[i0c], r0 = r[i0c];
+  real d0 = 0.0;
+  if constexpr (PC) d0 = dinv[i0c];
+  real pv[COSMO_PARTS_PER_THREAD];
+  partials_request(part_uc, n_uc, pv);
+  const CtlHead ch = ctl_head_load(ctl);
+  HEAD_ISSUED();
+  const real pa = partials_fold(pv, n_uc);
+  PIN_V4(u0, c0, x0, r0); PIN_V2(d0, pa); ctl_head_pin(ch);
+  if (guard && ch.halt) return;
+  if (ch.cg_done) return;
   __shared__ real red[COSMO_BS / 64];
-  if (k < 0) k = ctl->cg_kd;                     // device-side index: published by the k_cg_dirM in front (cg_k itself is rewritten below by workgroup 0)
-  const real res = ctl->resv[k & 1];
+  if (k < 0) k = ch.cg_kd;                       // device-side index: published by the k_cg_dirM in front (cg_k itself is rewritten below by workgroup 0)
+  const real res = (k & 1) ? ch.rv1 : ch.rv0;
   const real uc = block_sum(pa, red);
   real alpha = (res * res) / uc;
   if constexpr (PC) alpha = ctl->sr_gamma[k & 1] / uc;
