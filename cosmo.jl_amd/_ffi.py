@@ -24,6 +24,7 @@ PSD_TRIANGLE_COMPLEX = 10
 CUSTOM = 11
 KKT_CG, KKT_MINRES_REDUCED, KKT_MINRES, KKT_CG_SR, KKT_CG_JACOBI = 0, 1, 2, 3, 4
 KKT_DIRECT = 5          # QdldlKKTSolver: supernodal LDL' of the full KKT matrix on the device (csrc/ldl.hip)
+KKT_SCHUR = 6           # exact solve of the reduced system: block-diagonal part + dense capacitance inverse (csrc/schur.hip)
 STATUS_NAMES = {0: "Undetermined", 1: "Solved", 2: "Max_iter_reached", 3: "Unsolved", 4: "Primal_infeasible",
                 5: "Dual_infeasible", 6: "Time_limit_reached"}
 MAT_A, MAT_AT, MAT_P, MAT_OP = 0, 1, 2, 3
@@ -109,6 +110,10 @@ SIGNATURES = {
     "cosmo_hip_ldl_analyze": (C.c_int32, [C.c_int64, C.c_int64, _PI64, _PI64, _PI64, _PI64, _PI64, _PI64]),
     "cosmo_hip_set_kkt_perm": (C.c_int32, [C.c_void_p, C.c_int64, _PI64]),
     "cosmo_hip_direct_info": (C.c_int32, [C.c_void_p, _PI64]),
+    "cosmo_hip_set_schur_options": (C.c_int32, [C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_int32]),
+    "cosmo_hip_schur_analyze": (C.c_int32, [C.c_int64, C.c_int64, _PI64, _PI64, _PI64, _PI64, C.c_int32, _PI64]),
+    "cosmo_hip_schur_info": (C.c_int32, [C.c_void_p, _PI64]),
+    "cosmo_hip_schur_residual": (C.c_int32, [C.c_void_p, C.POINTER(C.c_double)]),
     "cosmo_hip_polar_dataflow_stats": (C.c_int32, [C.c_void_p, _PD]),
     "cosmo_hip_polar_dataflow_reset_timing": (C.c_int32, [C.c_void_p]),
     "cosmo_hip_get_kkt_solution": (C.c_int32, [C.c_void_p, _PR]),
@@ -184,6 +189,7 @@ SIGNATURES = {
     "cosmo_hip_batch_group_set_scaling_full": (C.c_int32, [C.c_void_p, C.c_int64, _PR, _PR, _PR, _PR, C.c_double, C.c_double]),
     "cosmo_hip_batch_group_set_accelerator": (C.c_int32, [C.c_void_p, C.POINTER(AccelParams)]),
     "cosmo_hip_batch_group_set_direct": (C.c_int32, [C.c_void_p, C.c_int32]),
+    "cosmo_hip_batch_group_set_schur_options": (C.c_int32, [C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_int32]),
     "cosmo_hip_batch_group_set_device_scaling": (C.c_int32, [C.c_void_p, C.c_int64, C.c_double, C.c_double]),
     "cosmo_hip_batch_group_get_scaling": (C.c_int32, [C.c_void_p, C.c_int64, _PR, _PR, _PD]),
     "cosmo_hip_batch_group_set_params": (C.c_int32, [C.c_void_p, C.POINTER(Params)]),
@@ -225,6 +231,25 @@ def ldl_analyze(n, m, P, A, perm=None, dtype=np.float64):
         raise CosmoHipError(rc, "cosmo_hip_ldl_analyze failed (bad pattern or permutation)")
     keys = ["nnz_L", "nnz_stored", "supernodes", "height", "max_width", "amalgamation_zeros", "panel_size", "update_pairs"]
     return dict(zip(keys, out.tolist()))
+
+
+SCHUR_PLAN_KEYS = ["nd", "components", "largest", "sum_size2", "nnz_W"]
+
+
+def schur_analyze(n, m, P, A, row_threshold=0, dtype=np.float64):
+    """cosmo_hip_schur_analyze: the split of the Schur-complement KKT solver on the host (no GPU needed).  P, A: scipy sparse (pattern only; stored
+    entries count, also explicit zeros).  Returns a dict with the eight figures of include/cosmo_hip.h."""
+    import scipy.sparse as sp
+    lib = load_library(dtype)
+    P = sp.csc_matrix(P); A = sp.csc_matrix(A)
+    Pp = P.indptr.astype(np.int64); Pi = P.indices.astype(np.int64)
+    Ap = A.indptr.astype(np.int64); Ai = A.indices.astype(np.int64)
+    out = np.zeros(8, dtype=np.int64)
+    ptr = lambda a: a.ctypes.data_as(_PI64)
+    rc = lib.cosmo_hip_schur_analyze(int(n), int(m), ptr(Pp), ptr(Pi), ptr(Ap), ptr(Ai), int(row_threshold), ptr(out))
+    if rc != 0:
+        raise CosmoHipError(rc, "cosmo_hip_schur_analyze failed (bad pattern)")
+    return dict(zip(SCHUR_PLAN_KEYS + ["dense_bytes", "accepted", "small_components"], out.tolist()))
 
 
 def load_library(dtype=np.float64):
@@ -582,6 +607,23 @@ class Handle:
         self._chk(self.lib.cosmo_hip_direct_info(self._h, out.ctypes.data_as(_PI64)))
         keys = ["nnz_L", "nnz_stored", "supernodes", "height", "max_width", "factorizations", "positive_pivots", "last_factor_ns"]
         return dict(zip(keys, out.tolist()))
+
+    def set_schur_options(self, row_threshold=0, nd_max=0, block_max=0, refine_steps=2):
+        """Options of the Schur-complement KKT solver (cosmo_hip_set_schur_options); they take effect at the next set_params with KKT_SCHUR.
+        0 keeps a default, except for refine_steps."""
+        self._chk(self.lib.cosmo_hip_set_schur_options(self._h, int(row_threshold), int(nd_max), int(block_max), int(refine_steps)))
+
+    def schur_info(self):
+        """Figures of the Schur-complement KKT solver (cosmo_hip_schur_info)."""
+        out = np.zeros(8, dtype=np.int64)
+        self._chk(self.lib.cosmo_hip_schur_info(self._h, out.ctypes.data_as(_PI64)))
+        return dict(zip(SCHUR_PLAN_KEYS + ["factorizations", "refine_steps_taken", "refine_steps_rejected"], out.tolist()))
+
+    def schur_residual(self):
+        """(||rhs - M x|| / ||rhs|| of the last solve, the same before refinement) (cosmo_hip_schur_residual)."""
+        out = np.zeros(2, dtype=np.float64)
+        self._chk(self.lib.cosmo_hip_schur_residual(self._h, out.ctypes.data_as(C.POINTER(C.c_double))))
+        return float(out[0]), float(out[1])
 
     def kkt_recurrence(self):
         """Which Krylov recurrence / kernels the KKT solves of this handle run (cosmo_hip_kkt_recurrence)."""
@@ -1055,6 +1097,10 @@ class BatchGroup:
 
     def warm_restart(self):
         self._chk(self.lib.cosmo_hip_batch_group_warm_restart(self._g))
+
+    def set_schur_options(self, row_threshold=0, nd_max=0, block_max=0, refine_steps=2):
+        """cosmo_hip_batch_group_set_schur_options: the options of the members that run KKT_SCHUR (on their own handles); before set_params."""
+        self._chk(self.lib.cosmo_hip_batch_group_set_schur_options(self._g, int(row_threshold), int(nd_max), int(block_max), int(refine_steps)))
 
     def get_qb(self, k):
         n, m = self.dims[int(k)]

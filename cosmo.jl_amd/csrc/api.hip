@@ -570,7 +570,7 @@ extern "C" int32_t cosmo_hip_set_params(cosmo_hip_handle* h, const cosmo_hip_par
   if (h->row_shard) return cosmo_fail(h, COSMO_HIP_ERR_UNSUPPORTED, "set_params: not available on a row-sharded handle");
   if (!p) return cosmo_fail(h, COSMO_HIP_ERR_INVALID, "null params");
   if (!h->have_cones) return cosmo_fail(h, COSMO_HIP_ERR_INVALID, "set_cones must be called before set_params");
-  if (p->kkt_kind < COSMO_HIP_KKT_CG || p->kkt_kind > COSMO_HIP_KKT_DIRECT) return cosmo_fail(h, COSMO_HIP_ERR_INVALID, "bad kkt_kind");
+  if (p->kkt_kind < COSMO_HIP_KKT_CG || p->kkt_kind > COSMO_HIP_KKT_SCHUR) return cosmo_fail(h, COSMO_HIP_ERR_INVALID, "bad kkt_kind");
   if (p->check_termination <= 0) return cosmo_fail(h, COSMO_HIP_ERR_INVALID, "check_termination must be > 0");
   if (p->adaptive_rho && p->adaptive_rho_interval == 0 && !(p->adaptive_rho_fraction >= 0.0 && p->setup_time >= 0.0))
     return cosmo_fail(h, COSMO_HIP_ERR_INVALID, "adaptive_rho_interval == 0 needs adaptive_rho_fraction >= 0 and setup_time >= 0");
@@ -625,6 +625,26 @@ extern "C" int32_t cosmo_hip_set_kkt_perm(cosmo_hip_handle* h, int64_t len, cons
   }
   h->kkt_perm.assign(perm, perm + len);
   return COSMO_HIP_OK;
+}
+
+extern "C" int32_t cosmo_hip_set_schur_options(cosmo_hip_handle* h, int32_t row_threshold, int64_t nd_max, int64_t block_max, int32_t refine_steps) {
+  ENTER(h);
+  if (row_threshold < 0 || row_threshold == 1 || nd_max < 0 || block_max < 0 || refine_steps < 0 || refine_steps > 8)
+    return cosmo_fail(h, COSMO_HIP_ERR_INVALID, "set_schur_options: row_threshold must be 0 (default) or >= 2, the limits >= 0 (0: default), refine_steps in 0 .. 8");
+  h->sc_row_threshold = row_threshold; h->sc_nd_max = nd_max; h->sc_block_max = block_max; h->sc_refine_steps = refine_steps;
+  return COSMO_HIP_OK;
+}
+
+extern "C" int32_t cosmo_hip_schur_info(cosmo_hip_handle* h, int64_t* out) {
+  ENTER(h);
+  if (!out) return cosmo_fail(h, COSMO_HIP_ERR_INVALID, "schur_info: null output");
+  return schur_info(h, out);
+}
+
+extern "C" int32_t cosmo_hip_schur_residual(cosmo_hip_handle* h, double* out) {
+  ENTER(h);
+  if (!out) return cosmo_fail(h, COSMO_HIP_ERR_INVALID, "schur_residual: null output");
+  return schur_residual(h, out);
 }
 
 extern "C" int32_t cosmo_hip_direct_info(cosmo_hip_handle* h, int64_t* out) {

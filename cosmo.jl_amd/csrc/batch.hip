@@ -3096,6 +3096,8 @@ extern "C" int32_t cosmo_hip_batch_set_params(cosmo_hip_batch* b, const cosmo_hi
   if (!b->have_cones) return bfail(b, COSMO_HIP_ERR_INVALID, "batch_set_cones first");
   for (int k = 0; k < b->nprob; ++k) if (!b->have[k]) return bfail(b, COSMO_HIP_ERR_INVALID, "problem %d not set", k);
   const bool direct = b->direct_on && p->kkt_kind == COSMO_HIP_KKT_DIRECT;
+  if (p->kkt_kind == COSMO_HIP_KKT_SCHUR)
+    return bfail(b, COSMO_HIP_ERR_UNSUPPORTED, "batch mode does not implement the Schur-complement KKT solver (kkt_kind SCHUR): a member with it runs on its own handle");
   if (p->kkt_kind != COSMO_HIP_KKT_CG && !direct)
     return bfail(b, COSMO_HIP_ERR_UNSUPPORTED, b->direct_on ? "batch mode implements the CG and the direct (DIRECT) KKT solvers"
                                                             : "batch mode implements the CG KKT solver (the direct one after cosmo_hip_batch_set_direct)");

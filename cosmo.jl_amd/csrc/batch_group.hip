@@ -61,6 +61,7 @@ struct cosmo_hip_batch_group {
   std::vector<GProblem> prob;
   std::vector<GClass> cls;
   bool finalized = false, aa_on = false;
+  bool schur_opts = false; int32_t sc_row_threshold = 0, sc_refine_steps = 2; int64_t sc_nd_max = 0, sc_block_max = 0;   // cosmo_hip_batch_group_set_schur_options
   bool direct_on = false;         // cosmo_hip_batch_group_set_direct: every class's batch takes kkt_kind DIRECT (cosmo_hip_batch_set_direct)
   // cosmo_hip_batch_group_set_device_scaling: set_params equilibrates every member without a caller's scaling on the device (cosmo_hip_batch_scale_ruiz
   // per class batch, cosmo_hip_scale_ruiz per member on its own handle)
@@ -179,6 +180,14 @@ extern "C" int32_t cosmo_hip_batch_group_set_direct(cosmo_hip_batch_group* g, in
   return COSMO_HIP_OK;
 }
 
+// cosmo_hip_set_schur_options for every member that runs kkt_kind SCHUR (always on its own handle); before set_params
+extern "C" int32_t cosmo_hip_batch_group_set_schur_options(cosmo_hip_batch_group* g, int32_t row_threshold, int64_t nd_max, int64_t block_max, int32_t refine_steps) {
+  if (!g) return COSMO_HIP_ERR_INVALID;
+  if (g->finalized) return gfail(g, COSMO_HIP_ERR_INVALID, "batch_group_set_schur_options: after set_params");
+  g->schur_opts = true; g->sc_row_threshold = row_threshold; g->sc_nd_max = nd_max; g->sc_block_max = block_max; g->sc_refine_steps = refine_steps;
+  return COSMO_HIP_OK;
+}
+
 // scale_ruiz! on the device for every member that has no caller's scaling (cosmo_hip_batch_group_set_scaling*): set_params then calls
 // cosmo_hip_batch_scale_ruiz on every class batch before cosmo_hip_batch_set_params and, for a member that runs on its own handle, cosmo_hip_scale_ruiz
 // before that handle's set_params.  iterations = 0 switches it off again.  Before set_params.
@@ -292,6 +301,7 @@ extern "C" int32_t cosmo_hip_batch_group_set_params(cosmo_hip_batch_group* g, co
         int32_t hr = cosmo_hip_create(&h, g->device);
         if (hr) return hbad(hr, nullptr, "cosmo_hip_create", k);
         C.hs.push_back(h);
+        if (g->schur_opts && (hr = cosmo_hip_set_schur_options(h, g->sc_row_threshold, g->sc_nd_max, g->sc_block_max, g->sc_refine_steps))) return hbad(hr, h, "set_schur_options", k);
         if ((hr = cosmo_hip_set_problem(h, p.n, p.m, p.Pp.data(), p.Pi.data(), p.Px.data(), p.Ap.data(), p.Ai.data(), p.Ax.data(), p.q.data(), p.b.data()))) return hbad(hr, h, "set_problem", k);
         if ((hr = cosmo_hip_set_cones_ex(h, (int64_t)p.ctype.size(), p.ctype.data(), p.cdim.data(), p.box_l.empty() ? nullptr : p.box_l.data(),
                                          p.box_u.empty() ? nullptr : p.box_u.data(), p.cparam.data()))) return hbad(hr, h, "set_cones", k);

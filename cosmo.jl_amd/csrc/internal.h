@@ -167,6 +167,7 @@ enum KernelClass {
 enum KktRoute {
   KKT_NONE = 0,
   KKT_DIRECT,             // supernodal LDL' of the full system (ldl.hip)
+  KKT_SCHUR,              // exact reduced solve: block-diagonal part + dense capacitance inverse (schur.hip)
   KKT_MINRES_FULL,        // MINRES on the full system (minres.hip)
   KKT_MINRES_REDUCED,     // MINRES on the reduced system (minres.hip)
   KKT_CG_PERSIST,         // literal CG in one persistent launch per solve (cg_persist.hip); falls back to KKT_CG_FUSED / KKT_CG_PLAIN
@@ -313,6 +314,11 @@ struct cosmo_hip_handle {
   void* ldl = nullptr;            // LdlPlan
   std::vector<int64_t> kkt_perm;  // cosmo_hip_set_kkt_perm (empty: the default ordering)
   long long ldl_analyses = 0;     // symbolic analyses this handle has run (ldl_build)
+  // Schur-complement KKT solver (schur.hip): plan, blocks and the dense capacitance inverse, built by set_params for kkt_kind COSMO_HIP_KKT_SCHUR
+  void* schur = nullptr;          // SchurDev
+  int sc_row_threshold = 0;       // cosmo_hip_set_schur_options (0: the defaults of schur_plan.h)
+  long long sc_nd_max = 0, sc_block_max = 0;
+  int sc_refine_steps = 2;        // SCHUR_REFINE_STEPS_DEFAULT
   // matrix value updates (cosmo_hip_update_matrices; update.hip).  Host maps from set_problem (value_maps.h) and build_op_split; their device copies
   // (u_*) and the staging of the new values are made by the first update, so a handle that never updates holds nothing of this on the device.
   std::vector<int> vm_A, vm_P, vm_PT;          // CSR entry of A / P / [P | A'] -> index in the caller's A_nzval / P_nzval
@@ -425,6 +431,16 @@ int32_t ldl_enqueue_refactor(cosmo_hip_handle* h, int cond);    // cond = 1: onl
 int32_t ldl_refactor_now(cosmo_hip_handle* h, bool inertia);
 int32_t ldl_enqueue_solve(cosmo_hip_handle* h, int guard, bool from_loop);
 int32_t ldl_info(cosmo_hip_handle* h, int64_t* out);
+
+// Schur-complement KKT solver (schur.hip)
+int32_t schur_setup(cosmo_hip_handle* h);                         // analysis, buffers, first factorisation (pivots checked)
+void schur_free(cosmo_hip_handle* h);
+int32_t schur_enqueue_refactor(cosmo_hip_handle* h, int cond);    // cond = 1: only if Ctl::rho_changed (the loop)
+int32_t schur_refactor_now(cosmo_hip_handle* h);
+int32_t schur_enqueue_solve(cosmo_hip_handle* h, int guard);      // x_tl = M^-1 rhs (rhs from enqueue_cg_rhs), refined
+int32_t schur_info(cosmo_hip_handle* h, int64_t* out);
+int32_t schur_residual(cosmo_hip_handle* h, double* out);
+bool schur_describe(const cosmo_hip_handle* h, char* buf, size_t len);
 
 // single-reduction CG (cg_sr.hip)
 int32_t sr_alloc(cosmo_hip_handle* h);

@@ -25,6 +25,7 @@ static KktRoute literal_route(const cosmo_hip_handle* h) { return h->cg_ru ? KKT
 void kkt_free(cosmo_hip_handle* h) {
   free_op_split(h);
   ldl_free(h);
+  schur_free(h);
   pcg_free(h);
   sr_free(h);
   h->route = KKT_NONE;
@@ -67,6 +68,7 @@ int32_t kkt_configure(cosmo_hip_handle* h, bool force_split) {
     pcg_free(h);
     sr_free(h);
     if (kind != COSMO_HIP_KKT_DIRECT) ldl_free(h);
+    schur_free(h);
     h->route = KKT_NONE;
     if (h->mr) { (void)hipFree(h->mr); h->mr = nullptr; }
     if (h->cg_ru) { (void)hipFree(h->cg_ru); h->cg_ru = nullptr; }
@@ -100,6 +102,10 @@ int32_t kkt_configure(cosmo_hip_handle* h, bool force_split) {
       // A refused factor stays readable through cosmo_hip_direct_info (positive pivots).
       h->route = KKT_DIRECT;
       return ldl_setup(h, h->kkt_perm);
+    case COSMO_HIP_KKT_SCHUR:
+      // exact solve of the reduced system (schur.hip): analysis, limits (UNSUPPORTED beyond them, no fallback), factorisation, pivot check
+      h->route = KKT_SCHUR;
+      return schur_setup(h);
     case COSMO_HIP_KKT_MINRES: h->route = KKT_MINRES_FULL; break;
     case COSMO_HIP_KKT_MINRES_REDUCED: h->route = KKT_MINRES_REDUCED; break;
     case COSMO_HIP_KKT_CG_JACOBI:
@@ -121,8 +127,8 @@ int32_t kkt_configure(cosmo_hip_handle* h, bool force_split) {
 }
 
 int32_t kkt_update_rho(cosmo_hip_handle* h) {
-  if (h->route != KKT_DIRECT) return refresh_op_split(h);
-  const int32_t rc = ldl_refactor_now(h, false);     // update_rho!(::QdldlKKTSolver): new values, refactor (:316-320)
+  if (h->route != KKT_DIRECT && h->route != KKT_SCHUR) return refresh_op_split(h);
+  const int32_t rc = h->route == KKT_SCHUR ? schur_refactor_now(h) : ldl_refactor_now(h, false);     // update_rho!(::QdldlKKTSolver): new values, refactor (:316-320)
   if (rc != COSMO_HIP_OK) { h->have_params = false; h->have_iterates = false; }    // a zero pivot leaves no usable factor
   return rc;
 }
@@ -139,6 +145,11 @@ int32_t kkt_update_values(cosmo_hip_handle* h) {
       if (rc != COSMO_HIP_OK) { h->have_params = false; h->have_iterates = false; }
       return rc;
     }
+    case KKT_SCHUR: {
+      const int32_t rc = schur_refactor_now(h);           // the maps read P.val / A.val themselves: refill, refactorise, pivot check
+      if (rc != COSMO_HIP_OK) { h->have_params = false; h->have_iterates = false; }
+      return rc;
+    }
     default:
       CHK(upd_refresh_operator(h));
       return refresh_op_split(h);      // k_op_refresh, k_fold_refresh, k_fold_dinv and the padded copy: the rho-dependent values
@@ -148,6 +159,7 @@ int32_t kkt_update_values(cosmo_hip_handle* h) {
 // rho may have changed on the device: the diagonal part of A' rho A follows (cheap, unconditional); the direct solver refills and
 // refactorises, each launch a no-op unless rho changed
 int32_t kkt_enqueue_refresh(cosmo_hip_handle* h) {
+  if (h->route == KKT_SCHUR) return schur_enqueue_refactor(h, 1);
   return h->route == KKT_DIRECT ? ldl_enqueue_refactor(h, 1) : refresh_op_split(h);
 }
 
@@ -186,6 +198,10 @@ static void pcg_fallback(cosmo_hip_handle* h) {
 int32_t kkt_enqueue_loop_solve(cosmo_hip_handle* h) {
   switch (h->route) {
     case KKT_DIRECT: return ldl_enqueue_solve(h, 1, true);
+    case KKT_SCHUR:          // the right-hand side of the CG routes, the exact solve, the tail; no Krylov budget
+      CHK(enqueue_cg_rhs(h, 1));
+      CHK(schur_enqueue_solve(h, 1));
+      return enqueue_tail(h, 1);
     case KKT_MINRES_FULL: case KKT_MINRES_REDUCED: return minres_enqueue_solve(h, 1, true);
     default: break;
   }
@@ -215,6 +231,12 @@ int32_t kkt_solve_now(cosmo_hip_handle* h) {
   switch (h->route) {
     case KKT_DIRECT: return ldl_enqueue_solve(h, 0, false);          // the full (n+m) system, as solve!(::QdldlKKTSolver) (kktsolver.jl:310-313)
     case KKT_MINRES_FULL: case KKT_MINRES_REDUCED: return minres_enqueue_solve(h, 0, false);
+    case KKT_SCHUR:
+      CHK(enqueue_y2_only(h));
+      CHK(enqueue_cg_rhs(h, 0));
+      CHK(schur_enqueue_solve(h, 0));
+      CHK(enqueue_tail(h, 0));
+      return enqueue_count_solve(h);
     default: break;
   }
   CHK(enqueue_y2_only(h));
@@ -239,7 +261,7 @@ int32_t kkt_solve_now(cosmo_hip_handle* h) {
 int32_t kkt_resume(cosmo_hip_handle* h, int extra) {
   CHK(enqueue_clear_stall(h));
   switch (h->route) {
-    case KKT_DIRECT: return COSMO_HIP_OK;        // no Krylov budget: a direct solve does not stall
+    case KKT_DIRECT: case KKT_SCHUR: return COSMO_HIP_OK;        // no Krylov budget: a direct solve does not stall
     case KKT_MINRES_FULL: case KKT_MINRES_REDUCED: return minres_resume(h, extra);
     case KKT_CG_PERSIST: pcg_fallback(h); break;
     default: break;
@@ -289,6 +311,7 @@ extern "C" const char* cosmo_hip_kkt_recurrence(cosmo_hip_handle* h) {
   switch (h->route) {
     case KKT_NONE: break;
     case KKT_DIRECT: return "direct: supernodal LDL' of the full KKT system, one launch per tree level (csrc/ldl.hip)";
+    case KKT_SCHUR: return schur_describe(h, buf, sizeof buf) ? buf : "not set up";
     case KKT_MINRES_FULL: return "minres on the full KKT system (csrc/minres.hip)";
     case KKT_MINRES_REDUCED: return "minres on the reduced system (csrc/minres.hip)";
     case KKT_CG_PERSIST: return "cg: literal recurrence in one persistent launch (csrc/cg_persist.hip, opt-in)";

@@ -65,6 +65,9 @@ extern "C" int32_t cosmo_hip_set_row_shard(cosmo_hip_handle* h, const int64_t* f
   if (hipSetDevice(h->device) != hipSuccess) return cosmo_fail(h, COSMO_HIP_ERR_HIP, "hipSetDevice failed");
   if (!h->have_params) return cosmo_fail(h, COSMO_HIP_ERR_INVALID, "set_row_shard: set_params first (the reduced operator is built from the whole A)");
   if (h->row_shard) return cosmo_fail(h, COSMO_HIP_ERR_INVALID, "set_row_shard: already row-sharded");
+  if (h->route == KKT_SCHUR)
+    return cosmo_fail(h, COSMO_HIP_ERR_UNSUPPORTED, "set_row_shard: the Schur-complement KKT solver (kkt_kind SCHUR) keeps the blocks of M_s and the dense "
+                      "capacitance inverse on one device; a sharded form is not implemented");
   if (h->route == KKT_DIRECT)
     return cosmo_fail(h, COSMO_HIP_ERR_UNSUPPORTED, "set_row_shard: the direct KKT solver (kkt_kind DIRECT) factorises the whole KKT matrix on one device; "
                       "a sharded factorisation is not implemented");

@@ -28,6 +28,7 @@ include("abi_structs.jl")
 
 const KKT_CG, KKT_MINRES_REDUCED, KKT_MINRES, KKT_CG_SR, KKT_CG_JACOBI = Int32(0), Int32(1), Int32(2), Int32(3), Int32(4)   # KKT_CG_SR: opt-in single-reduction CG; KKT_CG_JACOBI: opt-in Jacobi-preconditioned CG (assembled operator only)
 const KKT_DIRECT = Int32(5)   # QdldlKKTSolver on the device: supernodal LDL' of the full KKT matrix (csrc/ldl.hip)
+const KKT_SCHUR = Int32(6)    # opt-in exact solve of the reduced system: block-diagonal part + dense capacitance inverse (csrc/schur.hip)
 const STATUS = (:Undetermined, :Solved, :Max_iter_reached, :Unsolved, :Primal_infeasible, :Dual_infeasible, :Time_limit_reached)
 
 # the struct mirrors of abi_structs.jl were generated for ABI_VERSION: a library that reports another version would read / write them with a
@@ -225,7 +226,8 @@ mutable struct HipKKTSolver{T <: HipFloat} <: AbstractKKTSolver
     h::Handle{T}
     m::Int; n::Int
     function HipKKTSolver(P::SparseMatrixCSC{T, Int64}, A::SparseMatrixCSC{T, Int64}, sigma::T, rho;
-                          kind::Int32 = KKT_CG, device::Integer = 0, tol_constant = 1.0, tol_exponent = 1.5) where {T <: HipFloat}
+                          kind::Int32 = KKT_CG, device::Integer = 0, tol_constant = 1.0, tol_exponent = 1.5,
+                          row_threshold::Integer = 0, nd_max::Integer = 0, block_max::Integer = 0, refine_steps::Integer = 2) where {T <: HipFloat}
         m, n = size(A)
         h = Handle{T}(device)
         set_problem!(h, P, A, zeros(T, n), zeros(T, m))    # q, b are not needed by solve!
@@ -234,6 +236,10 @@ mutable struct HipKKTSolver{T <: HipFloat} <: AbstractKKTSolver
             (Ptr{Cvoid}, Int64, Ptr{Int32}, Ptr{Int64}, Ptr{T}, Ptr{T}), h.ptr, 1, types, dims, C_NULL, C_NULL))
         p = params_from(COSMO.Settings{T}(sigma = sigma), kind; tol_constant = tol_constant, tol_exponent = tol_exponent)
         rv = isa(rho, Number) ? fill(T(rho), m) : Vector{T}(rho)
+        if kind == KKT_SCHUR       # the options of the Schur-complement solver take effect at set_params!
+            check(h, ccall((:cosmo_hip_set_schur_options, lib(h)), Int32, (Ptr{Cvoid}, Int32, Int64, Int64, Int32), h.ptr,
+                Int32(row_threshold), Int64(nd_max), Int64(block_max), Int32(refine_steps)))
+        end
         set_params!(h, p, rv)
         new{T}(h, m, n)
     end
@@ -246,6 +252,23 @@ HipCGJacobiKKTSolver(P, A, sigma, rho; kwargs...) = HipKKTSolver(P, A, sigma, rh
 # QdldlKKTSolver (src/linear_solver/kktsolver.jl:285-320) on the device: set_params! analyses, factorises and throws "Objective function is not
 # convex." for a non-convex P; solve! solves the full (n+m) system, update_rho! refactorises
 HipQdldlKKTSolver(P, A, sigma, rho; kwargs...) = HipKKTSolver(P, A, sigma, rho; kind = KKT_DIRECT, kwargs...)
+# OPT-IN, no reference counterpart: an exact solve of the reduced system (block inverses + dense capacitance inverse + safeguarded refinement,
+# csrc/schur.hip); with_options(CosmoHIP.HipSchurKKTSolver, row_threshold = 3, refine_steps = 2).  set_params! throws beyond the size limits
+# (UNSUPPORTED) and on a non-positive pivot (non-convex P); update_rho! refactorises
+HipSchurKKTSolver(P, A, sigma, rho; kwargs...) = HipKKTSolver(P, A, sigma, rho; kind = KKT_SCHUR, kwargs...)
+
+# {nd, components, largest component, sum of size^2, nnz(M_s^-1 A_d'), factorisations, refinement steps kept in the last solve, steps rejected so far}
+function schur_info(S::HipKKTSolver)
+    out = zeros(Int64, 8)
+    GC.@preserve out check(S.h, ccall((:cosmo_hip_schur_info, lib(S.h)), Int32, (Ptr{Cvoid}, Ptr{Int64}), S.h.ptr, pointer(out)))
+    return out
+end
+# (||rhs - M x|| / ||rhs|| of the last solve, the same before refinement)
+function schur_residual(S::HipKKTSolver)
+    out = zeros(Float64, 2)
+    GC.@preserve out check(S.h, ccall((:cosmo_hip_schur_residual, lib(S.h)), Int32, (Ptr{Cvoid}, Ptr{Float64}), S.h.ptr, pointer(out)))
+    return (out[1], out[2])
+end
 
 # called from admm_x! (src/solver.jl:52): lhs = ws.sol, rhs = ws.ls, both length n+m and caller owned
 function solve!(S::HipKKTSolver{T}, lhs::AbstractVector{T}, rhs::AbstractVector{T}) where {T <: HipFloat}

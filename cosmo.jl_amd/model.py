@@ -34,7 +34,10 @@ QdldlKKTSolver = "QdldlKKTSolver"
 CGSingleReductionKKTSolver = "CGSingleReductionKKTSolver"
 # opt-in, no reference counterpart: Jacobi-preconditioned CG (IterativeSolvers' PCGIterable, Pl = diag of the reduced operator) on the assembled operator, csrc/cg_fold.hip
 CGJacobiKKTSolver = "CGJacobiKKTSolver"
-_KKT_KIND = {QdldlKKTSolver: _ffi.KKT_DIRECT, CGIndirectKKTSolver: _ffi.KKT_CG, MINRESIndirectKKTSolver: _ffi.KKT_MINRES, CGSingleReductionKKTSolver: _ffi.KKT_CG_SR, CGJacobiKKTSolver: _ffi.KKT_CG_JACOBI,
+# opt-in, no reference counterpart: an exact solve of the reduced system (block-diagonal part + dense capacitance inverse, Woodbury), csrc/schur.hip;
+# with_options(SchurComplementKKTSolver, row_threshold=3, refine_steps=2, nd_max=..., block_max=...)
+SchurComplementKKTSolver = "SchurComplementKKTSolver"
+_KKT_KIND = {SchurComplementKKTSolver: _ffi.KKT_SCHUR, QdldlKKTSolver: _ffi.KKT_DIRECT, CGIndirectKKTSolver: _ffi.KKT_CG, MINRESIndirectKKTSolver: _ffi.KKT_MINRES, CGSingleReductionKKTSolver: _ffi.KKT_CG_SR, CGJacobiKKTSolver: _ffi.KKT_CG_JACOBI,
              IndirectReducedKKTSolverMINRES: _ffi.KKT_MINRES_REDUCED}
 
 
@@ -395,6 +398,7 @@ class ResultInfo:
     max_norm_prim: float
     max_norm_dual: float
     rho_updates: List[float]
+    schur: Optional[dict] = None       # SchurComplementKKTSolver on a single handle: the figures of cosmo_hip_schur_info
 
 
 @dataclass
@@ -725,6 +729,15 @@ def update(model: Model, q=None, b=None, P=None, A=None):
         model.handle.update_qb(model.q if q is not None else None, model.b if b is not None else None)
 
 
+def _schur_options(kw):
+    """with_options(SchurComplementKKTSolver, ...) -> the arguments of set_schur_options"""
+    unknown = set(kw) - {"row_threshold", "nd_max", "block_max", "refine_steps"}
+    if unknown:
+        raise ValueError("SchurComplementKKTSolver: unknown options %s" % sorted(unknown))
+    return dict(row_threshold=int(kw.get("row_threshold", 0)), nd_max=int(kw.get("nd_max", 0)), block_max=int(kw.get("block_max", 0)),
+                refine_steps=int(kw.get("refine_steps", 2)))
+
+
 def _params_from_settings(h, st: Settings):
     p = _ffi.default_params()
     kkt = st.kkt_solver
@@ -739,6 +752,8 @@ def _params_from_settings(h, st: Settings):
         # the device LDL' (csrc/ldl.hip); with_options(QdldlKKTSolver, perm=...) supplies the ordering (perm[k] = original index at position k)
         if h is not None:
             h.set_kkt_perm(kw.get("perm"))
+    if kkt == SchurComplementKKTSolver and h is not None:
+        h.set_schur_options(**_schur_options(kw))
     p.tol_constant = float(kw.get("tol_constant", 1.0))
     p.tol_exponent = float(kw.get("tol_exponent", 1.5))
     p.sigma, p.alpha, p.rho = st.sigma, st.alpha, st.rho
@@ -918,6 +933,8 @@ def optimize(model: Model, dist=None, shard: str = "rows") -> Result:
         s, mu = dec.reverse(s, mu, complete_dual=model.settings.complete_dual)
     info = ResultInfo(r.r_prim, r.r_dual, r.max_norm_prim, r.max_norm_dual,
                       [r.rho_updates[i] for i in range(min(r.n_rho_updates, _ffi.MAX_RHO_UPDATES))])
+    if _KKT_KIND.get(model.settings.kkt_solver.solver if isinstance(model.settings.kkt_solver, OptionsFactory) else model.settings.kkt_solver) == _ffi.KKT_SCHUR:
+        info.schur = h.schur_info()
     times = ResultTimes(time.perf_counter() - t0, t_setup, r.iter_time, r.proj_time)
     return Result(x=x, y=-mu, s=s, obj_val=r.cost, iter=int(r.iter), status=_ffi.STATUS_NAMES[r.status], info=info,
                   times=times, kkt_iters_total=int(r.kkt_iters_total), safeguarding_iter=int(r.safeguarding_iter))
@@ -1117,6 +1134,8 @@ def prepare_batch_group(models: Sequence[Model], device: int):
             raise ValueError("optimize_batch: all problems of a batch share ONE Settings object (per-problem settings are not supported)")
     G = _ffi.BatchGroup(len(models), device, dtype=getattr(models[0], "dtype", np.float64))
     _install_accelerator(G, st)
+    if isinstance(st.kkt_solver, OptionsFactory) and st.kkt_solver.solver == SchurComplementKKTSolver:
+        G.set_schur_options(**_schur_options(st.kkt_solver.kwargs))      # such members run on their own handles (the batch kernels refuse the kind)
     if _direct_batch_of(st)[0]:
         G.set_direct(True)                                # every class's batch takes the LDL' form (default ordering: the classes differ in size)
     on_device = _batch_device_scaling_applies(models, st)

@@ -102,6 +102,16 @@ enum {
                                        changes, inertia-checked at setup ("Objective function is not convex.").  Supernodal and left-looking on the
                                        device (csrc/ldl.hip), symbolic analysis on the host (csrc/ldl_symbolic.cpp).  Opt-in; single-problem,
                                        unsharded handles only */
+  ,
+  COSMO_HIP_KKT_SCHUR = 6           /* OPT-IN: an EXACT solve of the reduced system (P + sigma I + A' rho A) x = rhs with the semantics of the
+                                       reference's default direct solver (factorise at setup, refactorise when rho changes; no Krylov tolerance,
+                                       no warm start).  The rows of A with at least row_threshold entries (A_d) are kept apart: the rest of the
+                                       matrix is block diagonal under a permutation, its blocks are inverted explicitly, and the dense capacitance
+                                       matrix diag(1 ./ rho_d) + A_d M_s^-1 A_d' is Cholesky-factored and inverted (Woodbury), followed by
+                                       safeguarded iterative refinement (csrc/schur.hip, analysis on the host in csrc/schur_plan.cpp).
+                                       cosmo_hip_set_params fails with UNSUPPORTED beyond the limits of cosmo_hip_set_schur_options and with INVALID
+                                       on a non-positive pivot (non-convex P).  Single-problem, unsharded handles only; batches run such a member on
+                                       its own handle */
 };
 
 /* ---- solver status (Result.status symbols, src/solver.jl:113,175,312,318,338,344,353) -------------- */
@@ -388,6 +398,25 @@ COSMO_HIP_API int32_t cosmo_hip_set_kkt_perm(cosmo_hip_handle* h, int64_t len, c
 /* out = {nnz(L), entries stored, supernodes, tree height, widest supernode, factorisations so far (setup, update_rho and in-loop refactorisations),
  * positive pivots of the last factorisation, wall time of the last factorisation outside the loop in ns}.  kkt_kind DIRECT only. */
 COSMO_HIP_API int32_t cosmo_hip_direct_info(cosmo_hip_handle* h, int64_t out[8]);
+
+/* ---- Schur-complement KKT solver (kkt_kind COSMO_HIP_KKT_SCHUR, csrc/schur.hip) ---- */
+/* Options of the next cosmo_hip_set_params with kkt_kind SCHUR.  row_threshold: a row of A with at least this many stored entries is kept out of the
+ * block-diagonal part (0: the default 3; 1 is invalid).  nd_max: most such rows accepted (0: the default 16384).  block_max: largest block of the
+ * block-diagonal part accepted (0: the default 256, which is also the kernels' bound: one thread per column of a block's inverse).  refine_steps: steps
+ * of iterative refinement per solve, 0 .. 8 (no zero-means-default; a fresh handle has 2).  Whatever the limits, the capacitance matrix and its inverse
+ * must fit 8 GiB together. */
+COSMO_HIP_API int32_t cosmo_hip_set_schur_options(cosmo_hip_handle* h, int32_t row_threshold, int64_t nd_max, int64_t block_max, int32_t refine_steps);
+/* The analysis alone, on the host (no handle, no device; P: n x n CSC, A: m x n CSC, 0-based, patterns only).  out = {nd = rows of A with at least
+ * row_threshold entries, connected components of the block-diagonal part, largest component, sum of size^2 over the components, nnz(M_s^-1 A_d'),
+ * bytes of the capacitance matrix plus its inverse in this library's scalar type, 1 if the default limits accept the problem (else 0), components of
+ * side <= 3}. */
+COSMO_HIP_API int32_t cosmo_hip_schur_analyze(int64_t n, int64_t m, const int64_t* P_colptr, const int64_t* P_rowval, const int64_t* A_colptr,
+                                              const int64_t* A_rowval, int32_t row_threshold, int64_t out[8]);
+/* out = {nd, components, largest component, sum of size^2, nnz(M_s^-1 A_d'), factorisations so far (setup, update_rho, update_matrices and in-loop
+ * refactorisations), refinement steps kept in the last solve, refinement steps the safeguard has rejected so far}.  kkt_kind SCHUR only. */
+COSMO_HIP_API int32_t cosmo_hip_schur_info(cosmo_hip_handle* h, int64_t out[8]);
+/* out = {||rhs - M x||_2 / ||rhs||_2 of the last solve, the same ratio before refinement}.  kkt_kind SCHUR only. */
+COSMO_HIP_API int32_t cosmo_hip_schur_residual(cosmo_hip_handle* h, double out[2]);
 /* Statistics of the device loop since set_iterates: out = {admm_iters, kkt_solves, kkt_iters_total,
  * kkt_budget_stalls, spmv_A_calls, spmv_AT_calls, spmv_P_calls, rho_updates}. */
 COSMO_HIP_API int32_t cosmo_hip_get_stats(cosmo_hip_handle* h, int64_t out[8]);
@@ -688,6 +717,8 @@ COSMO_HIP_API int32_t cosmo_hip_batch_group_get_rho_interval(cosmo_hip_batch_gro
  * one-problem classes -- all of them run in one host loop whose every launch covers them, workgroup c reading the descriptor of class c --, one per other batch
  * class, one per member that runs on its own handle), classes, problems, classes that ran inside a merged set} */
 COSMO_HIP_API int32_t cosmo_hip_batch_group_run_info(cosmo_hip_batch_group* g, int64_t out[5]);
+/* cosmo_hip_set_schur_options for the members that run kkt_kind SCHUR (each on its own handle: the batch kernels refuse the kind); before set_params */
+COSMO_HIP_API int32_t cosmo_hip_batch_group_set_schur_options(cosmo_hip_batch_group* g, int32_t row_threshold, int64_t nd_max, int64_t block_max, int32_t refine_steps);
 /* warm start of problem k (n, m, m entries; NULL = zeros); problems never set start from zero (src/solver.jl:128-129) */
 COSMO_HIP_API int32_t cosmo_hip_batch_group_set_iterates(cosmo_hip_batch_group* g, int64_t k, const cosmo_hip_real* x0, const cosmo_hip_real* s0, const cosmo_hip_real* mu0);
 /* optimize! for every problem; results has nprob entries in the caller's order */
