@@ -171,6 +171,9 @@ SIGNATURES = {
     "cosmo_hip_batch_update_qb": (C.c_int32, [C.c_void_p, C.c_int64, _PI64, _PR, _PR]),
     "cosmo_hip_batch_warm_restart": (C.c_int32, [C.c_void_p]),
     "cosmo_hip_batch_get_qb": (C.c_int32, [C.c_void_p, C.c_int64, _PR, _PR]),
+    "cosmo_hip_batch_update_qb_device": (C.c_int32, [C.c_void_p, C.c_int64, _PI64, _PR, _PR, C.c_void_p]),
+    "cosmo_hip_batch_set_iterates_device": (C.c_int32, [C.c_void_p, _PR, _PR, _PR, C.c_void_p]),
+    "cosmo_hip_batch_get_solution_device": (C.c_int32, [C.c_void_p, _PR, _PR, _PR, C.c_void_p]),
     "cosmo_hip_batch_stage_matrices": (C.c_int32, [C.c_void_p, C.c_int64, _PR, _PR, C.c_int32]),
     "cosmo_hip_batch_update_matrices": (C.c_int32, [C.c_void_p, C.c_int64, _PI64, _PR, _PR, C.c_int32]),
     "cosmo_hip_batch_update_matrices_info": (C.c_int32, [C.c_void_p, _PI64]),
@@ -311,6 +314,28 @@ def csc_julia(M, dtype=np.float64):
     rowval = np.ascontiguousarray(M.indices, dtype=np.int64) + 1
     nzval = np.ascontiguousarray(M.data, dtype=dtype)
     return colptr, rowval, nzval
+
+
+def check_device_tensor(t, shape, dtype, device, name="tensor"):
+    """The argument check of the device-memory entry points (Batch.update_qb_device, ...): `t` is a torch tensor of exactly `shape`, of the
+    library's element type `dtype` (numpy float64 / float32), contiguous, on `device` (a torch.device).  ValueError otherwise, before any
+    pointer reaches the library; None passes (the entry points take NULL)."""
+    if t is None:
+        return None
+    import torch
+    if not isinstance(t, torch.Tensor):
+        raise ValueError("%s must be a torch tensor on %s, got %s" % (name, device, type(t).__name__))
+    want = torch.float32 if _is_f32(dtype) else torch.float64
+    if t.dtype != want:
+        raise ValueError("%s has dtype %s, the batch computes in %s" % (name, t.dtype, want))
+    if tuple(t.shape) != tuple(int(v) for v in shape):
+        raise ValueError("%s has shape %s, expected %s" % (name, tuple(t.shape), tuple(int(v) for v in shape)))
+    if not t.is_contiguous():
+        raise ValueError("%s is not contiguous" % name)
+    dev = torch.device(device)
+    if t.device.type != dev.type or (dev.index is not None and t.device.index != dev.index):
+        raise ValueError("%s lives on %s, the batch on %s (device memory only: there is no host path behind this call)" % (name, t.device, dev))
+    return t
 
 
 def default_params(dtype=np.float64):
@@ -768,9 +793,40 @@ class Batch:
         if rc != OK:
             raise CosmoHipError(rc, "cosmo_hip_batch_create failed (no MI355X visible? this library has no CPU path)")
         self.nprob, self.n, self.m = int(nprob), int(n), int(m)
+        self.device = int(device)
 
     def _f(self, a, n=None, name="array"):
         return _f64(a, n, name, self.dtype)
+
+    def _t(self, t, shape, name):
+        """device pointer of a checked torch tensor (check_device_tensor), NULL for None"""
+        import torch
+        t = check_device_tensor(t, shape, self.dtype, torch.device("cuda", self.device), name)
+        return None if t is None else C.cast(C.c_void_p(t.data_ptr()), _PF if self.dtype == np.float32 else _PD)
+
+    def _stream(self, stream):
+        """the caller's hipStream_t: `stream` (a torch stream) or the current stream of the batch's device"""
+        import torch
+        s = torch.cuda.current_stream(self.device) if stream is None else stream
+        return C.c_void_p(s.cuda_stream)
+
+    def update_qb_device(self, q=None, b=None, members=None, stream=None):
+        """cosmo_hip_batch_update_qb_device: RAW q (len(members), n) and / or b (len(members), m) from torch tensors on the batch's device, applied at
+        once on the device; row j belongs to member members[j] (None: all members in order).  Ordered against `stream` (default: the current one)."""
+        mem = None if members is None else np.ascontiguousarray(members, dtype=np.int64).ravel()
+        cnt = self.nprob if mem is None else int(mem.size)
+        qp = self._t(q, (cnt, self.n), "q"); bp = self._t(b, (cnt, self.m), "b")
+        self._chk(self.lib.cosmo_hip_batch_update_qb_device(self._b, cnt, None if mem is None else mem.ctypes.data_as(_PI64), qp, bp, self._stream(stream)))
+
+    def set_iterates_device(self, x0=None, s0=None, y0=None, stream=None):
+        """cosmo_hip_batch_set_iterates_device: UNSCALED x0 (nprob, n), s0, y0 (nprob, m) from torch tensors (None: zeros), scaled on the device."""
+        xp = self._t(x0, (self.nprob, self.n), "x0"); sp_ = self._t(s0, (self.nprob, self.m), "s0"); yp = self._t(y0, (self.nprob, self.m), "y0")
+        self._chk(self.lib.cosmo_hip_batch_set_iterates_device(self._b, xp, sp_, yp, self._stream(stream)))
+
+    def get_solution_device(self, x=None, s=None, y=None, stream=None):
+        """cosmo_hip_batch_get_solution_device: the unscaled x (nprob, n), s, y (nprob, m) of all members into the given torch tensors (None: skip)."""
+        xp = self._t(x, (self.nprob, self.n), "x"); sp_ = self._t(s, (self.nprob, self.m), "s"); yp = self._t(y, (self.nprob, self.m), "y")
+        self._chk(self.lib.cosmo_hip_batch_get_solution_device(self._b, xp, sp_, yp, self._stream(stream)))
 
     def close(self):
         if self._b:

@@ -29,6 +29,7 @@
 #include "cone3.h"
 #include "batch_ldl.h"
 #include "batch_ruiz.h"
+#include "batch_devio.h"
 #include "value_maps.h"
 
 struct BCtl {                 // per problem, device resident
@@ -2351,6 +2352,9 @@ struct cosmo_hip_batch {
   const int32_t* d_umap = nullptr; const BUpdDesc* d_udesc = nullptr; unsigned char* d_mstage = nullptr;
   std::vector<int32_t> mstg_slot, mstg_mem, mstg_flag; std::vector<std::vector<real>> mstg_val;
   long long upd_count = 0, upd_last_bytes = 0, upd_map_bytes = 0, upd_factorisations = 0;
+  // device-memory inputs and results (cosmo_hip_batch_*_device, batch_devio.hip): the caller's stream is ordered against the batch's through these two
+  // events, created by the first such call (no timing)
+  hipEvent_t ev_in = nullptr, ev_out = nullptr;
 };
 
 static int32_t bfail(cosmo_hip_batch* b, int32_t code, const char* fmt, ...) {
@@ -2408,6 +2412,8 @@ extern "C" int32_t cosmo_hip_batch_destroy(cosmo_hip_batch* b) {
   for (void* p : b->allocs) (void)hipFree(p);
   bldl_free(b->ldl);
   if (b->h_state) (void)hipHostFree(b->h_state);
+  if (b->ev_in) (void)hipEventDestroy(b->ev_in);
+  if (b->ev_out) (void)hipEventDestroy(b->ev_out);
   if (b->stream) (void)hipStreamDestroy(b->stream);
   delete b;
   return COSMO_HIP_OK;
@@ -3843,6 +3849,109 @@ extern "C" int32_t cosmo_hip_batch_update_qb(cosmo_hip_batch* b, int64_t count, 
     if (rc) return rc;
   }
   return cosmo_hip_batch_apply_updates(b);
+}
+
+// ---- device-memory inputs and results (include/cosmo_hip.h: cosmo_hip_batch_update_qb_device; kernels in batch_devio.hip) ------------------------
+// A caller's pointer reaches a kernel only as device memory of the batch's device that holds `count` values from p on.
+static int32_t bdev_pointer(cosmo_hip_batch* b, const char* fn, const char* what, const void* p, size_t count) {
+  if (!p) return COSMO_HIP_OK;
+  hipPointerAttribute_t at;
+  memset(&at, 0, sizeof at);
+  if (hipPointerGetAttributes(&at, p) != hipSuccess) {
+    (void)hipGetLastError();                               // (an address the runtime does not know: the sticky error is this call's, not the batch's)
+    return bfail(b, COSMO_HIP_ERR_INVALID, "%s: %s is not device memory (hipPointerGetAttributes does not know the address)", fn, what);
+  }
+  if (at.type != hipMemoryTypeDevice) return bfail(b, COSMO_HIP_ERR_INVALID, "%s: %s is not device memory (memory type %d)", fn, what, (int)at.type);
+  if (at.device != b->device) return bfail(b, COSMO_HIP_ERR_INVALID, "%s: %s lives on device %d, the batch on device %d", fn, what, at.device, b->device);
+  hipDeviceptr_t base = nullptr; size_t size = 0;
+  if (hipMemGetAddressRange(&base, &size, (hipDeviceptr_t)const_cast<void*>(p)) != hipSuccess) { (void)hipGetLastError(); return COSMO_HIP_OK; }
+  const size_t off = (size_t)((const char*)p - (const char*)base);
+  if (off > size || count * sizeof(real) > size - off)
+    return bfail(b, COSMO_HIP_ERR_INVALID, "%s: %s needs %zu bytes, its allocation holds %zu from there on", fn, what, count * sizeof(real), off > size ? (size_t)0 : size - off);
+  return COSMO_HIP_OK;
+}
+
+// What every device entry point needs before it launches: the device, D / E / c on it (as stage_qb) and the two events.
+static int32_t bdev_init(cosmo_hip_batch* b) {
+  if (hipSetDevice(b->device) != hipSuccess) return bfail(b, COSMO_HIP_ERR_HIP, "hipSetDevice failed");
+  { const int32_t rc = bresident_init(b); if (rc) return rc; }
+  if (!b->ev_in) BHIP(b, hipEventCreateWithFlags(&b->ev_in, hipEventDisableTiming));
+  if (!b->ev_out) BHIP(b, hipEventCreateWithFlags(&b->ev_out, hipEventDisableTiming));
+  return COSMO_HIP_OK;
+}
+// the batch's stream starts behind what the caller's stream holds now ...
+static int32_t bdev_enter(cosmo_hip_batch* b, hipStream_t cs) {
+  BHIP(b, hipEventRecord(b->ev_in, cs));
+  BHIP(b, hipStreamWaitEvent(b->stream, b->ev_in, 0));
+  return COSMO_HIP_OK;
+}
+// ... and the caller's continues behind what the batch's holds now
+static int32_t bdev_leave(cosmo_hip_batch* b, hipStream_t cs) {
+  BHIP(b, hipEventRecord(b->ev_out, b->stream));
+  BHIP(b, hipStreamWaitEvent(cs, b->ev_out, 0));
+  return COSMO_HIP_OK;
+}
+
+extern "C" int32_t cosmo_hip_batch_update_qb_device(cosmo_hip_batch* b, int64_t count, const int64_t* members, const real* q_dev, const real* b_dev,
+                                                    void* stream) {
+  static const char* fn = "batch_update_qb_device";
+  if (!b || !b->finalized) return bfail(b, COSMO_HIP_ERR_INVALID, "%s: set_params first", fn);
+  if (count < 0 || count > b->nprob || (!members && count != b->nprob))
+    return bfail(b, COSMO_HIP_ERR_INVALID, "%s: count = %lld (0 <= count <= nprob = %d; without a member list count = nprob)", fn, (long long)count, b->nprob);
+  if (members) {
+    std::vector<char> seen((size_t)b->nprob, 0);
+    for (int64_t j = 0; j < count; ++j) {
+      const int64_t k = members[j];
+      if (k < 0 || k >= b->nprob) return bfail(b, COSMO_HIP_ERR_INVALID, "%s: member %lld out of range (0 <= k < %d)", fn, (long long)k, b->nprob);
+      if (seen[(size_t)k]) return bfail(b, COSMO_HIP_ERR_INVALID, "%s: member %lld is listed twice", fn, (long long)k);
+      seen[(size_t)k] = 1;
+    }
+  }
+  if (count == 0 || (!q_dev && !b_dev)) return COSMO_HIP_OK;
+  int32_t rc;
+  if ((rc = bdev_init(b))) return rc;
+  for (int64_t j = 0; j < count; ++j) {
+    const int64_t k = members ? members[j] : j;
+    if (b->stg_slot[(size_t)k] >= 0)
+      return bfail(b, COSMO_HIP_ERR_INVALID, "%s: member %lld has a host-staged q / b pending: apply_updates first", fn, (long long)k);
+  }
+  if ((rc = bdev_pointer(b, fn, "q", q_dev, (size_t)count * b->n)) || (rc = bdev_pointer(b, fn, "b", b_dev, (size_t)count * b->m))) return rc;
+  hipStream_t cs = (hipStream_t)stream;
+  if ((rc = bdev_enter(b, cs))) return rc;
+  BHIP(b, bdevio_update_qb(b->stream, (int)b->n, (int)b->m, (int)count, members, q_dev, b_dev, b->d_D, b->d_E, b->d_c, b->d_nonneg,
+                           (real)b->prm.cosmo_infty_min_scaling, const_cast<real*>(b->D.q), const_cast<real*>(b->D.b), const_cast<int*>(b->D.rho_cls)));
+  return bdev_leave(b, cs);
+}
+
+extern "C" int32_t cosmo_hip_batch_set_iterates_device(cosmo_hip_batch* b, const real* x0_dev, const real* s0_dev, const real* y0_dev, void* stream) {
+  static const char* fn = "batch_set_iterates_device";
+  if (!b || !b->finalized) return bfail(b, COSMO_HIP_ERR_INVALID, "%s: set_params first", fn);
+  int32_t rc;
+  if ((rc = bdev_init(b))) return rc;
+  const size_t Nn = (size_t)b->nprob * b->n, Nm = (size_t)b->nprob * b->m;
+  if ((rc = bdev_pointer(b, fn, "x0", x0_dev, Nn)) || (rc = bdev_pointer(b, fn, "s0", s0_dev, Nm)) || (rc = bdev_pointer(b, fn, "y0", y0_dev, Nm))) return rc;
+  hipStream_t cs = (hipStream_t)stream;
+  if ((rc = bdev_enter(b, cs))) return rc;
+  BHIP(b, bdevio_set_iterates(b->stream, b->nprob, (int)b->n, (int)b->m, x0_dev, s0_dev, y0_dev, b->D.Dinv, b->d_E, b->D.Einv, b->d_c, b->D.rho, b->D.w,
+                              b->D.w_prev, b->D.s));
+  if ((rc = bdev_leave(b, cs))) return rc;
+  BHIP(b, hipStreamSynchronize(b->stream));       // as cosmo_hip_batch_set_iterates: the control blocks are reset through the host
+  return brestart_state(b);
+}
+
+extern "C" int32_t cosmo_hip_batch_get_solution_device(cosmo_hip_batch* b, real* x_dev, real* s_dev, real* y_dev, void* stream) {
+  static const char* fn = "batch_get_solution_device";
+  if (!b || !b->finalized) return bfail(b, COSMO_HIP_ERR_INVALID, "%s: set_params first", fn);
+  if (!b->have_iterates) return bfail(b, COSMO_HIP_ERR_INVALID, "%s: the batch has no iterates yet (set_iterates, optimize)", fn);
+  int32_t rc;
+  if ((rc = bdev_init(b))) return rc;
+  const size_t Nn = (size_t)b->nprob * b->n, Nm = (size_t)b->nprob * b->m;
+  if ((rc = bdev_pointer(b, fn, "x", x_dev, Nn)) || (rc = bdev_pointer(b, fn, "s", s_dev, Nm)) || (rc = bdev_pointer(b, fn, "y", y_dev, Nm))) return rc;
+  hipStream_t cs = (hipStream_t)stream;
+  if ((rc = bdev_enter(b, cs))) return rc;
+  BHIP(b, bdevio_export_solution(b->stream, b->nprob, (int)b->n, (int)b->m, b->D.w_prev, b->D.s, b->D.mu, b->d_D, b->d_E, b->D.Einv, b->D.cinv, x_dev, s_dev,
+                                 y_dev));
+  return bdev_leave(b, cs);
 }
 
 extern "C" int32_t cosmo_hip_batch_warm_restart(cosmo_hip_batch* b) {

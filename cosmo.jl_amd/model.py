@@ -425,6 +425,22 @@ class Result:
 
 
 @dataclass
+class DeviceBatchResult:
+    """`BatchSolver.optimize(results="device")`: the unscaled solutions of all members as torch tensors on the batch's device -- x (nprob, n),
+    y (nprob, m), s (nprob, m), in the batch's dtype, valid on the stream that was current at the call -- and the per-member figures the solve
+    returns to the host anyway, as host arrays of nprob entries."""
+    x: object
+    y: object
+    s: object
+    status: List[str]
+    iter: np.ndarray
+    obj_val: np.ndarray
+    r_prim: np.ndarray
+    r_dual: np.ndarray
+    kkt_iters_total: np.ndarray
+
+
+@dataclass
 class ScaleMatrices:
     D: np.ndarray
     Dinv: np.ndarray
@@ -1235,7 +1251,11 @@ class BatchSolver:
     batch factorises the changed members again) and re-solves with the reference's second `optimize!` (src/setup.jl:18-62): no re-scaling, every rho vector and
     KKT factor kept, the accelerator restarted, status / iteration count / certificates / time limit fresh, and the iterates warm-started from the batch's
     own final ones on the device (warm_start="device") or from the models' x, s, mu (warm_start="models", e.g. after warm_start_primal).
-    Results are written back to the models as `optimize_batch` does.  `close()` releases the device batch and unbinds the models."""
+    Results are written back to the models as `optimize_batch` does.  `close()` releases the device batch and unbinds the models.
+
+    Data that already lives on the device needs no host copy (one structure only, not a mixed list): `update_device(q=, b=, members=)` takes torch
+    tensors, `optimize(x0=, s0=, y0=)` warm-starts from tensors and `optimize(results="device")` returns the solutions as tensors
+    (`DeviceBatchResult`); all of them are ordered on the current torch stream of the batch's device (csrc/batch_devio.hip)."""
 
     def __init__(self, models: Sequence[Model], device: Optional[int] = None, dist=None):
         if dist is not None and dist.get_world_size() > 1:
@@ -1272,36 +1292,95 @@ class BatchSolver:
             return                                        # not on the device yet: the first optimize uploads the model's P / A
         self._B.stage_matrices(k, P_vals, A_vals, apply_scaling=apply_scaling)
 
-    def optimize(self, warm_start: str = "device") -> List[Result]:
+    def update_device(self, q=None, b=None, members=None):
+        """New RAW q and / or b from torch tensors on the batch's device, without a host copy (cosmo_hip_batch_update_qb_device): q of shape
+        (len(members), n), b of shape (len(members), m), row j for member members[j]; members=None means all members in order.  The tensors have the
+        batch's dtype, are contiguous and live on its device (ValueError otherwise).  Applied at once, ordered behind the work already queued on the
+        current torch stream of that device; a listed member with an `update(model, q=, b=)` still staged is refused.  The models' host mirrors
+        `md.q` / `md.b` are left alone: after this call they no longer describe what the device solves."""
+        if self.models is None:
+            raise RuntimeError("BatchSolver: closed")
+        if self._B is None:
+            raise RuntimeError("BatchSolver.update_device: nothing is on the device before the first optimize()")
+        if self.mixed:
+            raise NotImplementedError("BatchSolver.update_device: a mixed list runs as a batch group, which takes no device arrays; use update(model, q=, b=)")
+        self._B.update_qb_device(q, b, members)
+
+    def _warm_start(self, warm_start, x0=None, s0=None, y0=None):
+        """The iterates and the restarted state of a re-solve: device tensors if any is given, else the batch's own or the models'."""
+        B, models = self._B, self.models
+        if x0 is not None or s0 is not None or y0 is not None:
+            B.set_iterates_device(x0, s0, y0)             # scale_variables! on the device (k_batch_set_iterates_dev)
+        elif warm_start == "device":
+            B.warm_restart()
+        else:                                             # scale_variables! (src/scaling.jl:118-123) of the models' iterates, as setup! does
+            xs = [md.sm.Dinv * md.x for md in models]; ss = [md.sm.E * md.s for md in models]; ms = [(md.sm.Einv * md.mu) * md.sm.c for md in models]
+            if self.mixed:
+                for k in range(len(models)):
+                    B.set_iterates(k, xs[k], ss[k], ms[k])
+            else:
+                B.set_iterates(np.concatenate(xs), np.concatenate(ss), np.concatenate(ms))
+
+    def optimize(self, warm_start: str = "device", results: str = "models", x0=None, s0=None, y0=None, out=None):
+        """Solve, or re-solve after updates.  warm_start: see the class.  x0 (nprob, n), s0, y0 (nprob, m): UNSCALED warm-start iterates as torch
+        tensors on the batch's device (a missing one counts as zeros); giving any of them replaces warm_start.  results="models" writes x, s, mu
+        into the models and returns one `Result` each; results="device" returns a `DeviceBatchResult` whose tensors are freshly allocated or the
+        triple out=(x, y, s), leaves the models' x, s, mu as they were and copies no iterate to the host."""
         import time
         if warm_start not in ("device", "models"):
             raise ValueError("BatchSolver.optimize: warm_start is 'device' or 'models'")
+        if results not in ("models", "device"):
+            raise ValueError("BatchSolver.optimize: results is 'models' or 'device'")
         if self.models is None:
             raise RuntimeError("BatchSolver: closed")
         t0 = time.perf_counter()
         models = self.models
-        if self._B is None:
+        from_device = x0 is not None or s0 is not None or y0 is not None
+        if self.mixed is None:
             _check_batch_psd_projection(models)
             self.mixed = len({_structure_key(md) for md in models}) > 1 or not _batch_kernels_take(models[0])
+        if self.mixed and (from_device or results == "device" or out is not None):
+            raise NotImplementedError("BatchSolver.optimize: a mixed list runs as a batch group, which takes and returns no device arrays")
+        if from_device or results == "device":
+            import torch
+            nprob, n, m = len(models), models[0].n, models[0].m
+            dev = torch.device("cuda", self.device)
+            for t, shape, name in ((x0, (nprob, n), "x0"), (s0, (nprob, m), "s0"), (y0, (nprob, m), "y0")):
+                _ffi.check_device_tensor(t, shape, models[0].dtype, dev, name)
+            if out is not None:
+                if results != "device" or len(out) != 3:
+                    raise ValueError("BatchSolver.optimize: out is a triple (x, y, s) of tensors for results='device'")
+                for t, shape, name in zip(out, ((nprob, n), (nprob, m), (nprob, m)), ("out x", "out y", "out s")):
+                    if t is None:
+                        raise ValueError("BatchSolver.optimize: %s is None" % name)
+                    _ffi.check_device_tensor(t, shape, models[0].dtype, dev, name)
+        elif out is not None:
+            raise ValueError("BatchSolver.optimize: out is a triple (x, y, s) of tensors for results='device'")
+        if self._B is None:
             self._B, self._st = prepare_batch_group(models, self.device) if self.mixed else prepare_batch(models, self.device, scaling_full=True)
+            if from_device:
+                self._warm_start(warm_start, x0, s0, y0)
             self.last_times = dict(setup_s=time.perf_counter() - t0)
         else:
-            B = self._B
-            B.apply_updates()                             # every staged q / b and P / A: one copy and one launch each per batch
+            self._B.apply_updates()                       # every staged q / b and P / A: one copy and one launch each per batch
             t1 = time.perf_counter()
-            if warm_start == "device":
-                B.warm_restart()
-            else:                                         # scale_variables! (src/scaling.jl:118-123) of the models' iterates, as setup! does
-                xs = [md.sm.Dinv * md.x for md in models]; ss = [md.sm.E * md.s for md in models]; ms = [(md.sm.Einv * md.mu) * md.sm.c for md in models]
-                if self.mixed:
-                    for k in range(len(models)):
-                        B.set_iterates(k, xs[k], ss[k], ms[k])
-                else:
-                    B.set_iterates(np.concatenate(xs), np.concatenate(ss), np.concatenate(ms))
+            self._warm_start(warm_start, x0, s0, y0)
             self.last_times = dict(apply_s=t1 - t0, restart_s=time.perf_counter() - t1)
         t_setup = time.perf_counter() - t0
         rs = self._B.optimize()
-        return _write_back(models, self._B, rs, self._st, self.mixed, t0, t_setup)
+        if results == "models":
+            return _write_back(models, self._B, rs, self._st, self.mixed, t0, t_setup)
+        if out is not None:
+            x, y, s = out
+        else:
+            dt = torch.float32 if models[0].dtype == np.float32 else torch.float64
+            x, y, s = (torch.empty((nprob, cols), dtype=dt, device=dev) for cols in (n, m, m))
+        self._B.get_solution_device(x=x, s=s, y=y)
+        for md in models:
+            md.is_optimized = True
+        return DeviceBatchResult(x=x, y=y, s=s, status=[_ffi.STATUS_NAMES[r.status] for r in rs], iter=np.array([r.iter for r in rs], dtype=np.int64),
+                                 obj_val=np.array([r.cost for r in rs]), r_prim=np.array([r.r_prim for r in rs]), r_dual=np.array([r.r_dual for r in rs]),
+                                 kkt_iters_total=np.array([r.kkt_iters_total for r in rs], dtype=np.int64))
 
     @property
     def batch(self):

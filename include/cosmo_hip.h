@@ -627,6 +627,30 @@ COSMO_HIP_API int32_t cosmo_hip_batch_apply_updates(cosmo_hip_batch* b);
 COSMO_HIP_API int32_t cosmo_hip_batch_update_qb(cosmo_hip_batch* b, int64_t count, const int64_t* members, const cosmo_hip_real* q, const cosmo_hip_real* bvec);
 COSMO_HIP_API int32_t cosmo_hip_batch_warm_restart(cosmo_hip_batch* b);
 COSMO_HIP_API int32_t cosmo_hip_batch_get_qb(cosmo_hip_batch* b, int64_t k, cosmo_hip_real* q /* n or NULL */, cosmo_hip_real* bvec /* m or NULL */);
+/* Device-memory inputs and results of a finalised batch: the same data as the calls above, read from and written to DEVICE arrays of the caller (memory
+ * of the batch's device, e.g. the storage of a tensor library that shares the HIP runtime), without a host copy.
+ * Stream contract: `stream` is the caller's HIP stream handle passed as void* (0 / NULL: the null stream).  The caller's arrays are produced on that stream
+ *   and consumed from it: every call records an event on `stream` and makes the batch's own stream wait for it, launches there, records a second event
+ *   on the batch's stream and makes `stream` wait for that one.  Work queued on `stream` before the call is therefore finished before the library reads,
+ *   and work queued on it after the call starts after the library has written; other streams must be ordered by the caller.  The two events belong to
+ *   the batch (created once, timing disabled).  update_qb_device and get_solution_device never synchronise the host; set_iterates_device does, for the
+ *   reset of the control state, exactly as cosmo_hip_batch_set_iterates.
+ * Validation, each answered with COSMO_HIP_ERR_INVALID and a message before anything is launched: the batch is finalised (set_params); every non-NULL
+ *   pointer is device memory of the batch's device according to hipPointerGetAttributes, in an allocation that holds the values read or written; see
+ *   the calls for the rest.
+ * cosmo_hip_batch_update_qb_device: cosmo_hip_batch_update_qb from device arrays, applied at once.  q_dev: count * n RAW values or NULL, b_dev: count * m
+ *   or NULL; row j belongs to batch member members[j].  members: HOST array of count indices, in range and without duplicates, or NULL = all members in
+ *   order (count = nprob).  Scaled and classified as cosmo_hip_batch_apply_updates does, bit for bit.  A listed member with a host-staged q / b pending is
+ *   refused ("apply_updates first"), so the order of two updates is never ambiguous; staged matrix values are left staged.
+ * cosmo_hip_batch_set_iterates_device: cosmo_hip_batch_set_iterates from UNSCALED device arrays x0 (nprob * n), s0, y0 (nprob * m; NULL = zeros): the
+ *   device applies scale_variables! (x = Dinv .* x0, s = E .* s0, mu = (Einv .* (-y0)) .* c) and forms w, w_prev, s; the state reset follows.
+ * cosmo_hip_batch_get_solution_device: the unscaled solution x = D .* x (nprob * n), s = Einv .* s, y = -((E .* mu) .* cinv) (nprob * m each) of all
+ *   members into the caller's arrays (NULL: skip); the batch must have iterates (set_iterates, optimize). */
+COSMO_HIP_API int32_t cosmo_hip_batch_update_qb_device(cosmo_hip_batch* b, int64_t count, const int64_t* members /* host, count or NULL */,
+                                                       const cosmo_hip_real* q_dev, const cosmo_hip_real* b_dev, void* stream);
+COSMO_HIP_API int32_t cosmo_hip_batch_set_iterates_device(cosmo_hip_batch* b, const cosmo_hip_real* x0_dev, const cosmo_hip_real* s0_dev,
+                                                          const cosmo_hip_real* y0_dev, void* stream);
+COSMO_HIP_API int32_t cosmo_hip_batch_get_solution_device(cosmo_hip_batch* b, cosmo_hip_real* x_dev, cosmo_hip_real* s_dev, cosmo_hip_real* y_dev, void* stream);
 /* New VALUES for the stored entries of P and / or A of members of a finalised batch (the counterpart of cosmo_hip_update_matrices): same pattern, in the
  * order of the P_nzval / A_nzval arrays cosmo_hip_batch_set_problem received for that member (NULL = unchanged).
  * cosmo_hip_batch_stage_matrices: after set_params (INVALID before it, or for k out of range); stages the values of member k on the host.  apply_scaling
