@@ -163,6 +163,7 @@ SIGNATURES = {
     "cosmo_hip_batch_get_counters": (C.c_int32, [C.c_void_p, _PI64]),
     "cosmo_hip_batch_kernel_info": (C.c_int32, [C.c_void_p, _PI64]),
     "cosmo_hip_batch_set_direct": (C.c_int32, [C.c_void_p, C.c_int32, _PI64]),
+    "cosmo_hip_batch_set_psd_side_max": (C.c_int32, [C.c_void_p, C.c_int32]),
     "cosmo_hip_batch_direct_info": (C.c_int32, [C.c_void_p, _PI64]),
     "cosmo_hip_batch_direct_counts": (C.c_int32, [C.c_void_p, _PI64]),
     "cosmo_hip_batch_set_scaling_full": (C.c_int32, [C.c_void_p, C.c_int64, _PR, _PR, _PR, _PR, C.c_double, C.c_double]),
@@ -192,6 +193,7 @@ SIGNATURES = {
     "cosmo_hip_batch_group_set_scaling_full": (C.c_int32, [C.c_void_p, C.c_int64, _PR, _PR, _PR, _PR, C.c_double, C.c_double]),
     "cosmo_hip_batch_group_set_accelerator": (C.c_int32, [C.c_void_p, C.POINTER(AccelParams)]),
     "cosmo_hip_batch_group_set_direct": (C.c_int32, [C.c_void_p, C.c_int32]),
+    "cosmo_hip_batch_group_set_psd_side_max": (C.c_int32, [C.c_void_p, C.c_int32]),
     "cosmo_hip_batch_group_set_schur_options": (C.c_int32, [C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_int32]),
     "cosmo_hip_batch_group_set_device_scaling": (C.c_int32, [C.c_void_p, C.c_int64, C.c_double, C.c_double]),
     "cosmo_hip_batch_group_get_scaling": (C.c_int32, [C.c_void_p, C.c_int64, _PR, _PR, _PD]),
@@ -981,6 +983,10 @@ class Batch:
             raise ValueError("perm needs n + m = %d entries" % (self.n + self.m))
         self._chk(self.lib.cosmo_hip_batch_set_direct(self._b, 1 if on else 0, p.ctypes.data_as(_PI64)))
 
+    def set_psd_side_max(self, side):
+        """cosmo_hip_batch_set_psd_side_max: the largest PSD cone side set_cones accepts (64 .. 256, default 64); before set_cones."""
+        self._chk(self.lib.cosmo_hip_batch_set_psd_side_max(self._b, int(side)))
+
     def direct_info(self):
         """Figures of the batch's direct KKT solver (cosmo_hip_batch_direct_info)."""
         out = np.zeros(8, dtype=np.int64)
@@ -1124,6 +1130,10 @@ class BatchGroup:
     def set_direct(self, on=True):
         """cosmo_hip_batch_group_set_direct: every class's batch takes kkt_kind DIRECT (default ordering); before set_params."""
         self._chk(self.lib.cosmo_hip_batch_group_set_direct(self._g, 1 if on else 0))
+
+    def set_psd_side_max(self, side):
+        """cosmo_hip_batch_group_set_psd_side_max: every class's batch accepts PSD cones up to this side (64 .. 256, default 64); before set_params."""
+        self._chk(self.lib.cosmo_hip_batch_group_set_psd_side_max(self._g, int(side)))
 
     def set_device_scaling(self, iterations, min_scaling=1e-4, max_scaling=1e4):
         """cosmo_hip_batch_group_set_device_scaling: set_params equilibrates every member without a caller's scaling on the device; before set_params."""

@@ -10,7 +10,8 @@
 // Cone support in batch mode: ZeroSet, Nonnegatives, Box, SecondOrderCone and PsdCone / PsdConeTriangle of side <= 64 (round 4: side <= 16 by the
 // wave-level Jacobi projection of psd16.h, 17 .. 64 by the workgroup-level block Jacobi of psdwg.h -- the routines the single-problem path uses for
 // such cones, called from the problem's persistent workgroup: batches of small SDPs, src/convexset.jl:402-412 inside the composite projection
-// :885-891) and ExponentialCone / PowerCone / their duals (cone3.h, one thread per cone); larger PSD cones take the single-problem path.  The
+// :885-891) and ExponentialCone / PowerCone / their duals (cone3.h, one thread per cone); larger PSD cones take the single-problem path -- or, after
+// cosmo_hip_batch_set_psd_side_max, stay here up to side 256: the same block Jacobi with the block pairs of a tournament step in rounds (psdwg.h).  The
 // infeasibility certificates run between persistent launches (k_batch_inf_capture / k_batch_inf_check below).
 // Accelerator (round 4): with cosmo_hip_batch_set_accelerator the loop is the reference's accelerated loop (src/solver.jl:140-165,
 // src/accelerator_interface.jl:58-116) per problem -- Anderson update / accelerate, safeguarding, deferred rho updates and certificates -- all inside
@@ -208,7 +209,7 @@ __device__ __forceinline__ void batch_project_psd_mid(const BatchDev& D, int k, 
     const int d = D.mid_d[cI], kind = D.mid_kind[cI], ld = D.mid_ld[cI], ncp = D.mid_ncp[cI];
     real* xc = x + D.mid_off[cI];
     const real c = psdwg_populate<BS>(xc, d, kind, ld, ncp, R(1.0), 0, g, red);
-    (void)psdwg_jacobi<4>(g, ld, ncp / 8, d, c, R(0.125), 0, ws_base, any_rot);
+    (void)psdwg_jacobi_batch(g, ld, ncp / 8, d, c, R(0.125), ws_base, any_rot);     // (<= 4 block pairs: one per wave; more: in rounds)
     __syncthreads();
     (void)psdwg_finish<BS>(xc, d, kind, ld, ncp, c, g, 0, red);
   }
@@ -2062,7 +2063,7 @@ __device__ __forceinline__ void batch_inf_check_body(const BatchDev& D, const in
       real* g = D.psdG + (long long)k * D.psdG_stride + D.mid_goff[cI];
       const int d = D.mid_d[cI], kind = D.mid_kind[cI], ld = D.mid_ld[cI], ncp = D.mid_ncp[cI];
       const real c = psdwg_populate<BS>(v + D.mid_off[cI], d, kind, ld, ncp, sign, 1, g, red);
-      (void)psdwg_jacobi<4>(g, ld, ncp / 8, d, c, R(0.125), 0, psd_ws, &flag2);
+      (void)psdwg_jacobi_batch(g, ld, ncp / 8, d, c, R(0.125), psd_ws, &flag2);
       __syncthreads();
       const real lm = psdwg_finish<BS>(v + D.mid_off[cI], d, kind, ld, ncp, c, g, 1, red);
       if (!(lm > -tol)) bad = 1;
@@ -2333,6 +2334,7 @@ struct cosmo_hip_batch {
   std::vector<uint32_t> h_slA, h_slT; std::vector<real> h_pdiag; std::vector<unsigned char> h_pdiag_has;
   // direct KKT solver (cosmo_hip_batch_set_direct): the switch, the requested ordering (empty: default) and the plan built by set_params
   bool direct_on = false; std::vector<int64_t> direct_perm; BLdlPlan* ldl = nullptr;
+  int psd_side_max = 64;      // cosmo_hip_batch_set_psd_side_max: the largest PSD cone side set_cones accepts (64 .. 256; above 64 the block pairs run in rounds, psdwg.h)
   // resident re-solves (cosmo_hip_batch_stage_qb / apply_updates / warm_restart): D, E, c themselves (set_scaling_full; else the reciprocals of the
   // inverses), their device copies and the per-row Nonnegatives flag (uploaded by the first update); the staged raw vectors, one slot per member
   std::vector<real> hD, hE, hc;
@@ -2505,7 +2507,7 @@ extern "C" int32_t cosmo_hip_batch_set_cones_ex(cosmo_hip_batch* b, int64_t ncon
       long long d = 0;
       if (type[k] == COSMO_HIP_PSD_SQUARE) { while ((d + 1) * (d + 1) <= dim[k]) ++d; if (d * d != dim[k]) return bfail(b, COSMO_HIP_ERR_INVALID, "PsdCone: dimension %lld is not a square", (long long)dim[k]); }
       else { while ((d + 1) * (d + 2) / 2 <= dim[k]) ++d; if (d * (d + 1) / 2 != dim[k]) return bfail(b, COSMO_HIP_ERR_INVALID, "PsdConeTriangle: dimension %lld is not triangular", (long long)dim[k]); }
-      if (d > 64) return bfail(b, COSMO_HIP_ERR_UNSUPPORTED, "batch mode projects PSD cones of side <= 64 (side %lld: use one handle per problem)", d);
+      if (d > b->psd_side_max) return bfail(b, COSMO_HIP_ERR_UNSUPPORTED, "batch mode projects PSD cones of side <= %d (side %lld: use one handle per problem)", b->psd_side_max, d);
     } else if (type[k] >= COSMO_HIP_EXP && type[k] <= COSMO_HIP_DUAL_POW) {
       if (dim[k] != 3) return bfail(b, COSMO_HIP_ERR_INVALID, "exponential / power cones have dimension 3");
       if (type[k] == COSMO_HIP_POW || type[k] == COSMO_HIP_DUAL_POW) {
@@ -3602,6 +3604,17 @@ extern "C" int32_t cosmo_hip_batch_get_iterates(cosmo_hip_batch* b, int64_t k, r
   if (w_prev) BHIP(b, hipMemcpy(w_prev, b->D.w_prev + (size_t)k * N, N * sizeof(real), hipMemcpyDeviceToHost));
   if (s) BHIP(b, hipMemcpy(s, b->D.s + (size_t)k * m, m * sizeof(real), hipMemcpyDeviceToHost));
   if (mu) BHIP(b, hipMemcpy(mu, b->D.mu + (size_t)k * m, m * sizeof(real), hipMemcpyDeviceToHost));
+  return COSMO_HIP_OK;
+}
+
+// The largest PSD cone side cosmo_hip_batch_set_cones accepts: 64 (the default) .. 256.  Above 64 a tournament step has more block pairs than the four
+// waves / workspaces every batch kernel guarantees, and each wave visits its pairs in rounds (psdwg.h: psdwg_jacobi_rounds); G costs ld * ncp reals per
+// cone and member in global memory (512 KB at side 256 in double precision).  Before set_cones.
+extern "C" int32_t cosmo_hip_batch_set_psd_side_max(cosmo_hip_batch* b, int32_t side) {
+  if (!b) return COSMO_HIP_ERR_INVALID;
+  if (b->have_cones || b->finalized) return bfail(b, COSMO_HIP_ERR_INVALID, "batch_set_psd_side_max: call before batch_set_cones (the cones are checked against the limit there)");
+  if (side < 64 || side > 256) return bfail(b, COSMO_HIP_ERR_INVALID, "batch_set_psd_side_max: side %d is outside 64 .. 256", (int)side);
+  b->psd_side_max = (int)side;
   return COSMO_HIP_OK;
 }
 

@@ -63,6 +63,7 @@ struct cosmo_hip_batch_group {
   bool finalized = false, aa_on = false;
   bool schur_opts = false; int32_t sc_row_threshold = 0, sc_refine_steps = 2; int64_t sc_nd_max = 0, sc_block_max = 0;   // cosmo_hip_batch_group_set_schur_options
   bool direct_on = false;         // cosmo_hip_batch_group_set_direct: every class's batch takes kkt_kind DIRECT (cosmo_hip_batch_set_direct)
+  int32_t psd_side_max = 64;      // cosmo_hip_batch_group_set_psd_side_max: the limit every class's batch checks its PSD cones against (cosmo_hip_batch_set_psd_side_max)
   // cosmo_hip_batch_group_set_device_scaling: set_params equilibrates every member without a caller's scaling on the device (cosmo_hip_batch_scale_ruiz
   // per class batch, cosmo_hip_scale_ruiz per member on its own handle)
   bool ruiz_on = false; int64_t ruiz_iterations = 0; double ruiz_min = 0.0, ruiz_max = 0.0;
@@ -180,6 +181,16 @@ extern "C" int32_t cosmo_hip_batch_group_set_direct(cosmo_hip_batch_group* g, in
   return COSMO_HIP_OK;
 }
 
+// the largest PSD cone side of every class's batch (cosmo_hip_batch_set_psd_side_max: 64 .. 256, default 64); before set_params.  Classes the batch
+// kernels still refuse keep their own handles.
+extern "C" int32_t cosmo_hip_batch_group_set_psd_side_max(cosmo_hip_batch_group* g, int32_t side) {
+  if (!g) return COSMO_HIP_ERR_INVALID;
+  if (g->finalized) return gfail(g, COSMO_HIP_ERR_INVALID, "batch_group_set_psd_side_max: after set_params");
+  if (side < 64 || side > 256) return gfail(g, COSMO_HIP_ERR_INVALID, "batch_group_set_psd_side_max: side " + std::to_string(side) + " is outside 64 .. 256");
+  g->psd_side_max = side;
+  return COSMO_HIP_OK;
+}
+
 // cosmo_hip_set_schur_options for every member that runs kkt_kind SCHUR (always on its own handle); before set_params
 extern "C" int32_t cosmo_hip_batch_group_set_schur_options(cosmo_hip_batch_group* g, int32_t row_threshold, int64_t nd_max, int64_t block_max, int32_t refine_steps) {
   if (!g) return COSMO_HIP_ERR_INVALID;
@@ -259,6 +270,7 @@ extern "C" int32_t cosmo_hip_batch_group_set_params(cosmo_hip_batch_group* g, co
         if (rc) return bad(rc, "batch_set_scaling");
       }
     }
+    if (g->psd_side_max != 64) { rc = cosmo_hip_batch_set_psd_side_max(C.b, g->psd_side_max); if (rc) return bad(rc, "batch_set_psd_side_max"); }
     rc = cosmo_hip_batch_set_cones_ex(C.b, (int64_t)p0.ctype.size(), p0.ctype.data(), p0.cdim.data(), bl.data(), bu.data(), p0.cparam.data());
     if (rc == COSMO_HIP_OK && g->aa_on) rc = cosmo_hip_batch_set_accelerator(C.b, &g->aa);
     if (rc == COSMO_HIP_OK && g->direct_on) rc = cosmo_hip_batch_set_direct(C.b, 1, nullptr);

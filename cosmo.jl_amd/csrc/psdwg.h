@@ -1,8 +1,8 @@
 // psdwg.h -- workgroup-level PSD projection of ONE cone with 16 < d <= 256 by block one-sided (Hestenes) Jacobi on G = X + c I with the Gram /
 // update products on the matrix cores (src/convexset.jl:219-263: X+ = sum_{lambda > 0} lambda z z'; the design is described at the top of psd.hip).
 // Shared by the single-problem path (psd.hip: k_psd_jacobi_wg, one workgroup per cone) and -- round 4 -- by the persistent workgroups of the batch
-// kernels (batch.hip: PSD cones of side 17 .. 64 of a batch of small SDPs), which run populate -> sweeps -> column scaling -> SYRK for one cone after
-// the other with all their waves.
+// kernels (batch.hip: PSD cones of side 17 .. 64 of a batch of small SDPs, up to side 256 after cosmo_hip_batch_set_psd_side_max), which run populate ->
+// sweeps -> column scaling -> SYRK for one cone after the other with all their waves.
 #pragma once
 #include "psd16.h"
 
@@ -168,6 +168,63 @@ __device__ __forceinline__ int psdwg_jacobi(real* __restrict__ g, int ld, int nb
     __syncthreads();
   }
   return sweep;
+}
+
+// The same process for nb / 2 >= NW block pairs per tournament step (batch kernels, side 65 .. 256): the block pairs of one step -- and of the diagonal
+// pass -- are disjoint in their columns, so wave wv visits pairs wv, wv + NW, wv + 2 NW, ... of the step one after the other on its one workspace.
+// Visits, barriers between the steps, any_rot, PSD_MAX_SWEEPS, tol and tiny as above; every loop is bounded by nb.
+template <int NW>
+__device__ __forceinline__ int psdwg_jacobi_rounds(real* __restrict__ g, int ld, int nb, int d, real c, real tolf, unsigned char* ws_base, int* any_rot) {
+  const int lane = threadIdx.x & 63, wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);      // (wave-uniform: the pair arithmetic of the rounds stays scalar)
+  const int npairs = nb / 2;
+  const real tol = tolf * (real)d * PSD_EPS;
+  const real tiny = (tol * c) * (tol * c);
+  const PsdWgWs ws = psdwg_ws_at(ws_base + (size_t)(wv < NW ? wv : 0) * PSDWG_WS_STRIDE);
+  real* W = ws.w.W; real* J = ws.w.J;
+  int sweep = 0;
+  auto visit = [&](int I, int Jb, int full) {
+    if (lane < 16) ws.cols[lane] = (lane < 8) ? (I * 8 + lane) : (Jb * 8 + lane - 8);
+    wave_lds_fence();
+    const int colL = ws.cols[lane & 15];
+    const v4d w = panel_gram(g, ld, colL, 0, ld, lane);
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int i = ACC_ROW(lane, r), j = lane & 15;
+      W[i * WLD + j] = w[r];
+      J[i * WLD + j] = (i == j) ? 1.0 : 0.0;
+    }
+    wave_lds_fence();
+    if (!gram_needs_work(W, tol, tiny, !full, lane)) return;
+    if (jacobi16_sweep(W, J, ws.w.part, ws.w.ca, ws.w.cb, tol, tiny, 0, full ? 15 : 8, lane)) {
+      real jt[4];
+#pragma unroll
+      for (int t = 0; t < 4; ++t) jt[t] = J[((lane >> 4) + 4 * t) * WLD + (lane & 15)];
+      panel_update(g, ld, ws.cols, jt, 0, ld, lane);
+      if (lane == 0) *any_rot = 1;
+    }
+  };
+  for (; sweep < PSD_MAX_SWEEPS; ++sweep) {
+    if (threadIdx.x == 0) *any_rot = 0;
+    __syncthreads();
+    for (int st = -1; st < nb - 1; ++st) {                // st = -1: the diagonal pass, all pairs inside blocks (2w, 2w+1); then the tournament steps
+      if (wv < NW)
+        for (int w = wv; w < npairs; w += NW) {
+          int I = 2 * w, Jb = 2 * w + 1;
+          if (st >= 0) rr_pair(nb, st, w, I, Jb);
+          visit(I, Jb, st < 0);
+          wave_lds_fence();                               // (the workspace is reused by this wave's next pair)
+        }
+      __syncthreads();
+    }
+    if (!*any_rot) break;
+    __syncthreads();
+  }
+  return sweep;
+}
+// the form a batch kernel with four guaranteed waves / workspaces calls for one cone: the one-pair-per-wave process up to side 64 (its bits unchanged)
+__device__ __forceinline__ int psdwg_jacobi_batch(real* __restrict__ g, int ld, int nb, int d, real c, real tolf, unsigned char* ws_base, int* any_rot) {
+  if (nb / 2 <= 4) return psdwg_jacobi<4>(g, ld, nb, d, c, tolf, 0, ws_base, any_rot);
+  return psdwg_jacobi_rounds<4>(g, ld, nb, d, c, tolf, ws_base, any_rot);
 }
 
 // ---- the other three phases for ONE cone handled by a whole workgroup of BS threads (batch kernels) -----------------------------------------------

@@ -129,6 +129,13 @@ class Settings:
     # one factor per member in its persistent workgroup, refactorised there when its rho changes -- same statuses and solutions to solver accuracy as
     # the single handle, not the same bits.  With persistent_kernel=True it also routes optimize() of one small model to that form.
     direct_batch: bool = False
+    # PSD cones of side 65 .. 256 in batch mode (not a field of COSMO.Settings): the batch kernels take PSD cones up to this side (64 .. 256).  At the
+    # default a member with a larger cone gets its own single-problem handle inside the batch group (its own chain of launches per iteration); with a
+    # larger limit it stays in the persistent batch kernels, whose block Jacobi then visits the block pairs of a tournament step in rounds (csrc/psdwg.h),
+    # and a BatchSolver over such models is a resident single-structure batch (update_device, results="device", update(P=, A=), device Ruiz scaling).
+    # Same statuses and solutions to solver accuracy as the own handle, not the same bits: that handle projects by the sign iteration by default, the
+    # batch kernels by block Jacobi.  Opt-in because a batch of very few such members is slower this way ("PSD cones of side 65 to 256").
+    batch_psd_side_max: int = 64
     # scale_ruiz! of a whole batch on the device (not a field of COSMO.Settings): optimize_batch, BatchSolver and persistent_kernel otherwise equilibrate
     # every member on the host, one model at a time.  True: the members are uploaded unscaled and one launch scales them all (csrc/batch_ruiz.hip,
     # cosmo_hip_batch_scale_ruiz), when scaling != 0 and every member that still needs scaling has a symmetric P -- otherwise the host path, silently,
@@ -1036,6 +1043,8 @@ def prepare_batch(models: Sequence[Model], device: int, scaling_full: bool = Fal
     direct, perm = _direct_batch_of(st)
     if direct:
         B.set_direct(True, perm)                          # before set_params: the LDL' form of the batch kernels (csrc/batch_ldl.hip)
+    if _batch_psd_side_max_of(st) != 64:
+        B.set_psd_side_max(_batch_psd_side_max_of(st))    # before set_cones: PSD cones up to that side stay in the batch kernels (csrc/psdwg.h)
     bl, bu = [], []
     on_device = not _host_scaling and _batch_device_scaling_applies(models, st)
     pending = []                                         # members the device pass scales (uploaded unscaled, no set_scaling*)
@@ -1104,22 +1113,32 @@ def _fits_persistent_kernel(md: Model) -> bool:
     return image <= 150 * 1024 and md.A.nnz <= 65535 and md.P.nnz <= 65535
 
 
+def _batch_psd_side_max_of(st: Settings) -> int:
+    """Settings.batch_psd_side_max, checked: the library takes 64 .. 256 (cosmo_hip_batch_set_psd_side_max)."""
+    side = int(st.batch_psd_side_max)
+    if not 64 <= side <= 256:
+        raise ValueError("Settings.batch_psd_side_max is %d: the batch kernels take a limit of 64 .. 256" % side)
+    return side
+
+
 def _check_batch_psd_projection(models) -> None:
-    """psd_projection = "eigen" in batch mode: the persistent kernels project cones of side <= 64 by Jacobi eigensolvers anyway; a member with a larger
-    cone would run on a group-internal handle, which has no such switch."""
+    """psd_projection = "eigen" in batch mode: the persistent kernels project cones of side <= Settings.batch_psd_side_max (default 64) by Jacobi
+    eigensolvers anyway; a member with a larger cone would run on a group-internal handle, which has no such switch."""
     for md in models:
         if md.settings.psd_projection == "eigen":
+            lim = _batch_psd_side_max_of(md.settings)
             for K in md.sets:
                 if K.kind in (_ffi.PSD_SQUARE, _ffi.PSD_TRIANGLE):
                     d = int(round(np.sqrt(K.dim))) if K.kind == _ffi.PSD_SQUARE else int((np.sqrt(1 + 8 * K.dim) - 1) // 2)
-                    if d > 64:
-                        raise NotImplementedError("optimize_batch with psd_projection='eigen' and a PSD cone of side %d > 64: solve such models with optimize()" % d)
+                    if d > lim:
+                        raise NotImplementedError("optimize_batch with psd_projection='eigen' and a PSD cone of side %d > %d: solve such models with optimize()" % (d, lim))
 
 
 def _batch_kernels_take(md: Model) -> bool:
     """What cosmo_hip_batch_* accepts (csrc/batch.hip): CG solver kinds (and QdldlKKTSolver with Settings.direct_batch), the cone types of batch mode with
-    PSD cones of side <= 64, a fixed rho interval."""
+    PSD cones of side <= Settings.batch_psd_side_max (default 64), a fixed rho interval."""
     st = md.settings
+    side_max = _batch_psd_side_max_of(st)
     kkt = st.kkt_solver.solver if isinstance(st.kkt_solver, OptionsFactory) else st.kkt_solver
     kinds = (CGIndirectKKTSolver, CGSingleReductionKKTSolver, CGJacobiKKTSolver) + ((QdldlKKTSolver,) if st.direct_batch else ())
     if kkt not in kinds or (st.adaptive_rho and st.adaptive_rho_interval == 0):
@@ -1130,7 +1149,7 @@ def _batch_kernels_take(md: Model) -> bool:
     for K in md.sets:
         if K.kind in (_ffi.PSD_SQUARE, _ffi.PSD_TRIANGLE):
             d = int(round(np.sqrt(K.dim))) if K.kind == _ffi.PSD_SQUARE else int((np.sqrt(1 + 8 * K.dim) - 1) // 2)
-            if d > 64:
+            if d > side_max:
                 return False
         elif K.kind not in (_ffi.ZERO, _ffi.NONNEG, _ffi.BOX, _ffi.SOC, _ffi.EXP, _ffi.DUAL_EXP, _ffi.POW, _ffi.DUAL_POW):
             return False
@@ -1154,6 +1173,8 @@ def prepare_batch_group(models: Sequence[Model], device: int):
         G.set_schur_options(**_schur_options(st.kkt_solver.kwargs))      # such members run on their own handles (the batch kernels refuse the kind)
     if _direct_batch_of(st)[0]:
         G.set_direct(True)                                # every class's batch takes the LDL' form (default ordering: the classes differ in size)
+    if _batch_psd_side_max_of(st) != 64:
+        G.set_psd_side_max(_batch_psd_side_max_of(st))    # every class's batch takes PSD cones up to that side
     on_device = _batch_device_scaling_applies(models, st)
     pending = []                                          # members the device pass of set_params scales (uploaded unscaled, no set_scaling*)
     if on_device:
@@ -1197,7 +1218,7 @@ def _solve_shard_on_device(models: Sequence[Model], device: int) -> List[Result]
         return []
     _check_batch_psd_projection(models)
     t0 = time.perf_counter()
-    # one structure the persistent kernels take -> the batch directly; anything else (several structures, a PSD cone of side > 64, a MINRES solver kind,
+    # one structure the persistent kernels take -> the batch directly; anything else (several structures, a PSD cone of side > batch_psd_side_max, a MINRES solver kind,
     # the automatic rho interval) -> the group, which gives every structure class its batch or, where the batch kernels refuse, one handle per problem
     mixed = len({_structure_key(md) for md in models}) > 1 or not _batch_kernels_take(models[0])
     B, st = prepare_batch_group(models, device) if mixed else prepare_batch(models, device)
@@ -1211,6 +1232,7 @@ def _solve_shard_on_device(models: Sequence[Model], device: int) -> List[Result]
         LAST_BATCH_INFO["own_handle_members"] = int(np.sum(B.class_info(with_modes=True)[2] == 1))     # members the batch kernels refused
     else:
         LAST_BATCH_INFO["kernel_form"] = B.kernel_info()["form"]      # which form of the batch kernels ran (cosmo_hip_batch_kernel_info)
+        LAST_BATCH_INFO["own_handle_members"] = 0                     # one structure the batch kernels take: no member has a handle of its own
     if not mixed and _direct_batch_of(st)[0]:
         LAST_BATCH_INFO["direct_info"] = B.direct_info()               # the LDL' form of the batch kernels ran (csrc/batch_ldl.hip)
         LAST_BATCH_INFO["direct_counts"] = B.direct_counts()

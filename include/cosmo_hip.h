@@ -549,7 +549,8 @@ COSMO_HIP_API int32_t cosmo_hip_batch_set_problem(cosmo_hip_batch* b, int64_t k,
                                     const cosmo_hip_real* P_nzval, const int64_t* A_colptr, const int64_t* A_rowval,
                                     const cosmo_hip_real* A_nzval, const cosmo_hip_real* q, const cosmo_hip_real* bvec);
 /* cone structure shared by all problems; box_l / box_u hold nprob * (#Box rows) entries, problem-major.  Cone kinds of batch mode: ZeroSet,
- * Nonnegatives, Box, SecondOrderCone, PsdCone / PsdConeTriangle of side <= 64 (src/convexset.jl:25-28, 71-74, 100-114, 303-321, 402-412, 844-847)
+ * Nonnegatives, Box, SecondOrderCone, PsdCone / PsdConeTriangle of side <= 64 (src/convexset.jl:25-28, 71-74, 100-114, 303-321, 402-412, 844-847;
+ * up to side 256 after cosmo_hip_batch_set_psd_side_max)
  * and, through cosmo_hip_batch_set_cones_ex, the exponential / power cones; anything else returns COSMO_HIP_ERR_UNSUPPORTED (one handle per
  * problem serves it) */
 COSMO_HIP_API int32_t cosmo_hip_batch_set_cones(cosmo_hip_batch* b, int64_t ncones, const int32_t* type, const int64_t* dim,
@@ -602,6 +603,13 @@ COSMO_HIP_API int32_t cosmo_hip_batch_get_iterates(cosmo_hip_batch* b, int64_t k
  * memory), and INVALID with "Objective function is not convex. (member k)" when a member's first factorisation has not exactly n positive pivots.
  * A zero or non-finite pivot later in the loop stops that member; cosmo_hip_batch_optimize then returns INVALID naming it.  Call before set_params. */
 COSMO_HIP_API int32_t cosmo_hip_batch_set_direct(cosmo_hip_batch* b, int32_t on, const int64_t* perm /* NULL or n + m */);
+/* The largest PsdCone / PsdConeTriangle side cosmo_hip_batch_set_cones accepts: side in 64 .. 256 (anything else: INVALID), default 64.  Opt-in: up to
+ * side 64 a tournament step of the block Jacobi has at most four block pairs, one per guaranteed wave; above it every wave visits its pairs of a step in
+ * rounds, and G takes ld * ncp values per cone and member in device memory (512 KB at side 256 in double precision).  set_cones refuses only sides above
+ * the chosen limit (UNSUPPORTED, naming it).  Projections and certificates of cones of side <= 64 keep their bits whatever the limit.  A member solved this
+ * way agrees with its own single-problem handle to solver accuracy, not to the bit (that handle projects by the matrix-sign iteration by default).
+ * Call before cosmo_hip_batch_set_cones. */
+COSMO_HIP_API int32_t cosmo_hip_batch_set_psd_side_max(cosmo_hip_batch* b, int32_t side);
 /* out = {nnz(L), panel values per problem, supernodes, tree height, widest supernode, analysis time in ns, factorisations of all members together,
  * smallest positive-pivot count of the members' last factorisations} */
 COSMO_HIP_API int32_t cosmo_hip_batch_direct_info(cosmo_hip_batch* b, int64_t out[8]);
@@ -724,6 +732,9 @@ COSMO_HIP_API int32_t cosmo_hip_batch_group_set_scaling_full(cosmo_hip_batch_gro
 COSMO_HIP_API int32_t cosmo_hip_batch_group_set_accelerator(cosmo_hip_batch_group* g, const cosmo_hip_accel_params* p);
 /* cosmo_hip_batch_set_direct(on, default ordering) for every class's batch; before set_params.  Classes the batch kernels still refuse keep their own handles */
 COSMO_HIP_API int32_t cosmo_hip_batch_group_set_direct(cosmo_hip_batch_group* g, int32_t on);
+/* cosmo_hip_batch_set_psd_side_max(side) for every class's batch (64 .. 256, default 64); before set_params.  Classes the batch kernels still refuse keep
+ * their own handles */
+COSMO_HIP_API int32_t cosmo_hip_batch_group_set_psd_side_max(cosmo_hip_batch_group* g, int32_t side);
 /* Device Ruiz equilibration for the group (before set_params; iterations = 0: off): cosmo_hip_batch_group_set_params then calls
  * cosmo_hip_batch_scale_ruiz on every class batch before cosmo_hip_batch_set_params and cosmo_hip_scale_ruiz on every member that runs on its own handle
  * before that handle's set_params.  Members for which cosmo_hip_batch_group_set_scaling* was called keep the caller's scaling.
