@@ -166,6 +166,8 @@ SIGNATURES = {
     "cosmo_hip_batch_set_psd_side_max": (C.c_int32, [C.c_void_p, C.c_int32]),
     "cosmo_hip_batch_direct_info": (C.c_int32, [C.c_void_p, _PI64]),
     "cosmo_hip_batch_direct_counts": (C.c_int32, [C.c_void_p, _PI64]),
+    "cosmo_hip_batch_polish": (C.c_int32, [C.c_void_p, C.c_double, C.c_int32]),
+    "cosmo_hip_batch_polish_info": (C.c_int32, [C.c_void_p, _PI32, _PD]),
     "cosmo_hip_batch_set_scaling_full": (C.c_int32, [C.c_void_p, C.c_int64, _PR, _PR, _PR, _PR, C.c_double, C.c_double]),
     "cosmo_hip_batch_stage_qb": (C.c_int32, [C.c_void_p, C.c_int64, _PR, _PR]),
     "cosmo_hip_batch_apply_updates": (C.c_int32, [C.c_void_p]),
@@ -999,6 +1001,33 @@ class Batch:
         out = np.zeros(self.nprob, dtype=np.int64)
         self._chk(self.lib.cosmo_hip_batch_direct_counts(self._b, out.ctypes.data_as(_PI64)))
         return out
+
+    def polish(self, delta=1e-6, refine_iter=3):
+        """cosmo_hip_batch_polish: the active-set polish of every member the last optimize() reported Solved (csrc/batch_polish.hip)."""
+        self._chk(self.lib.cosmo_hip_batch_polish(self._b, float(delta), int(refine_iter)))
+
+    def polish_info(self, status_out=None):
+        """cosmo_hip_batch_polish_info: dict of arrays over the members -- status (1 accepted, -1 rejected, 0 not attempted), r_prim_before,
+        r_dual_before, r_prim, r_dual and cost of the candidate, active_rows.  status_out: an int32 torch tensor of nprob entries on the batch's device
+        receives the statuses without a host copy (the dict then has no "status")."""
+        out = np.zeros(6 * self.nprob, dtype=np.float64)
+        if status_out is not None:
+            import torch
+            if not (isinstance(status_out, torch.Tensor) and status_out.dtype == torch.int32 and status_out.is_contiguous() and status_out.numel() == self.nprob
+                    and status_out.device == torch.device("cuda", self.device)):
+                raise ValueError("polish_info: status_out is a contiguous int32 tensor of %d entries on cuda:%d" % (self.nprob, self.device))
+            sp_ = C.cast(C.c_void_p(status_out.data_ptr()), _PI32)
+            self._chk(self.lib.cosmo_hip_batch_polish_info(self._b, sp_, out.ctypes.data_as(_PD)))
+            st = None
+        else:
+            st = np.zeros(self.nprob, dtype=np.int32)
+            self._chk(self.lib.cosmo_hip_batch_polish_info(self._b, st.ctypes.data_as(_PI32), out.ctypes.data_as(_PD)))
+        q = out[:4 * self.nprob].reshape(self.nprob, 4)
+        d = dict(r_prim_before=q[:, 0].copy(), r_dual_before=q[:, 1].copy(), r_prim=q[:, 2].copy(), r_dual=q[:, 3].copy(),
+                 active_rows=out[4 * self.nprob:5 * self.nprob].astype(np.int64), cost=out[5 * self.nprob:].copy())
+        if st is not None:
+            d["status"] = st
+        return d
 
     def accel_stats(self):
         """Per problem: dict of int64 arrays (accelerated, accepted, declined, restarts, active, safeguarding_iter)."""

@@ -28,17 +28,12 @@
 #include "psd16.h"
 #include "psdwg.h"
 #include "cone3.h"
+#include "batch_dev.h"
 #include "batch_ldl.h"
 #include "batch_ruiz.h"
 #include "batch_devio.h"
+#include "batch_polish.h"
 #include "value_maps.h"
-
-struct BCtl {                 // per problem, device resident
-  int status; int n_rho_updates;
-  long long iter, solves, kkt_iters_total;
-  real rho, cost, r_prim, r_dual, max_norm_prim, max_norm_dual;
-  real rho_updates[COSMO_HIP_MAX_RHO_UPDATES];
-};
 
 // Per-problem state of the Anderson accelerator (k_batch_admm*<..., AA = true>; csrc/anderson.hip is the single-problem form of the same
 // algorithm).  R: the mem x mem triangular factor, column-major with leading dimension BAA_MEM.
@@ -51,9 +46,6 @@ struct BAa {
   real eta[BAA_MEM];
   real R[BAA_MEM * BAA_MEM];
 };
-
-struct BMat { const int* rowptr; const int* col; const real* val; const int* split; const int* rb;   // concatenated over problems
-              const long long* nz_off; const int* rb_off; const int* nb; int nrows; int split_col; };
 
 struct BatchDev {
   int nprob; int n; int m;
@@ -100,29 +92,6 @@ struct BParams {
   real aa_tau, aa_eta_max, aa_start_acc;  // safeguard_tol; eta_max; AccuracyActivation (< 0: unused)
 };
 
-__device__ __forceinline__ CsrView bview(const BMat& M, int k) {
-  CsrView v;
-  v.rowptr = M.rowptr + (long long)k * (M.nrows + 1);
-  v.col = M.col + M.nz_off[k];
-  v.val = M.val + M.nz_off[k];
-  v.split = M.split ? M.split + (long long)k * M.nrows : nullptr;
-  v.rb = M.rb + M.rb_off[k];
-  v.nb = M.nb[k];
-  v.nrows = M.nrows;
-  v.split_col = M.split_col;
-  return v;
-}
-
-__device__ __forceinline__ real proj_simple(real x, uint32_t meta, const real* bl, const real* bu) {
-  const uint32_t kind = meta & 3u;
-  if (kind == 0u) return x;
-  if (kind == 1u) return 0.0;
-  if (kind == 2u) return (x != x) ? x : ((x > R(0.0)) ? x : R(0.0));
-  const uint32_t j = meta >> 2;
-  const real l = bl[j], u = bu[j];
-  return (x < l) ? l : ((x > u) ? u : x);
-}
-
 // ---------------------------------------------------------------------------------------------------------------------
 // Two ways of applying a problem's matrices inside its workgroup; both give every row to one thread that adds the row's
 // products left to right (the order of Julia's CSC kernels), and both visit the rows in the order of the same tile
@@ -135,46 +104,8 @@ __device__ __forceinline__ real proj_simple(real x, uint32_t meta, const real* b
 //               A' as (u16 position into A's values, u16 row) so the values are held once, P, the tile descriptors and
 //               the two gathered vectors -- and every product of every iteration reads LDS only.  BASELINE config 3
 //               (n = 500, m = 1000, nnz = 10 000) needs 157 KB of the CU's 160 KB.  HBM then only sees the iterates.
+// bsum / bsum_db / bmax, bview, proj_simple and StreamOps itself: batch_dev.h (shared with batch_polish.hip).
 // ---------------------------------------------------------------------------------------------------------------------
-template <int BS>
-__device__ __forceinline__ real bsum(real v, real* red) {
-  v = wave_sum(v);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  real t = 0.0;
-#pragma unroll
-  for (int i = 0; i < BS / 64; ++i) t += red[i];
-  return t;
-}
-// Block sum with ONE barrier: consecutive calls alternate between two sets of BS / 64 slots (ph flips).  The set written now was last read two
-// calls ago, and every thread has passed the barrier of the call in between since then, so no barrier is needed in front of the writes.  Callers
-// put a workgroup barrier between the last classic bsum / bmax on `red` and the first bsum_db (the classic ones start with their own barrier, so
-// the other direction needs nothing).  Same additions in the same order as bsum.
-template <int BS>
-__device__ __forceinline__ real bsum_db(real v, real* red, int& ph) {
-  v = wave_sum(v);
-  real* r = red + ph * (BS / 64);
-  ph ^= 1;
-  if ((threadIdx.x & 63) == 0) r[threadIdx.x >> 6] = v;
-  __syncthreads();
-  real t = 0.0;
-#pragma unroll
-  for (int i = 0; i < BS / 64; ++i) t += r[i];
-  return t;
-}
-template <int BS>
-__device__ __forceinline__ real bmax(real v, real* red) {
-  v = wave_max(v);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  real t = red[0];
-#pragma unroll
-  for (int i = 1; i < BS / 64; ++i) t = (red[i] > t || red[i] != red[i]) ? red[i] : t;
-  return t;
-}
-
 #define PSD16_WS_STRIDE PSDWG_WS_STRIDE      // one per-wave workspace layout for both uses (psdwg.h: the psd16.h workspace + the panel's column list)
 // the PSD cones (side <= 16) of a problem: waves 0 .. nws-1 take the cones round-robin, each on its own LDS workspace.  x = the projected slack
 // (global memory, or its LDS staging copy in the register kernel).  Callers put a workgroup barrier in front and behind.
@@ -215,27 +146,6 @@ __device__ __forceinline__ void batch_project_psd_mid(const BatchDev& D, int k, 
   }
 }
 
-struct StreamOps {
-  CsrView A, AT, PT;
-  real* lds; real* red;
-  unsigned char* psd_ws;
-  static constexpr bool in_lds = false;
-  __device__ __forceinline__ real rowA(int, const real*) const { return R(0.0); }     // (register-CG form: LdsOps only)
-  __device__ __forceinline__ real rowAT(int, const real*) const { return R(0.0); }
-  __device__ __forceinline__ real rowP(int, const real*) const { return R(0.0); }
-  __device__ __forceinline__ real* buf_n(real* g) const { return g; }       // vector the A / P products gather from
-  __device__ __forceinline__ real* buf_m(real* g) const { return g; }       // vector the A' products gather from
-  __device__ __forceinline__ const real* stage_n(const real* g) const { return g; }
-  template <class F> __device__ __forceinline__ void rows_A(const real* x, F fn) {
-    for (int t = 0; t < A.nb; ++t) csr_stream_tile(A, x, x, t, lds, red, fn);
-  }
-  template <class F> __device__ __forceinline__ void rows_AT(const real* y, F fn) {
-    for (int t = 0; t < AT.nb; ++t) csr_stream_tile(AT, y, y, t, lds, red, fn);
-  }
-  template <class F> __device__ __forceinline__ void rows_PT(const real* x1, const real* x2, F fn) {
-    for (int t = 0; t < PT.nb; ++t) csr_stream_tile(PT, x1, x2, t, lds, red, fn);
-  }
-};
 
 // ---- hand-scheduled row loops of the register kernel's Krylov passes (round 5) --------------------------------------------------------------
 // A row product needs per nonzero t:  P(t) an index load (u16 column position of A, or the packed u32 pair of A'), G(t) two b64 loads whose
@@ -2357,6 +2267,10 @@ struct cosmo_hip_batch {
   // device-memory inputs and results (cosmo_hip_batch_*_device, batch_devio.hip): the caller's stream is ordered against the batch's through these two
   // events, created by the first such call (no timing)
   hipEvent_t ev_in = nullptr, ev_out = nullptr;
+  // active-set polish (cosmo_hip_batch_polish, batch_polish.h): the statuses the last cosmo_hip_batch_optimize reported (empty: no solve yet); the
+  // descriptor with the polish's own slabs and vectors, allocated by the first call; the plan it built itself when the batch has no direct solver
+  std::vector<int> last_status, pol_elig;
+  BPolishDev pol; BLdlPlan* pol_plan = nullptr; int* d_pol_elig = nullptr; int pol_grid = 0; bool pol_ready = false, pol_ran = false;
 };
 
 static int32_t bfail(cosmo_hip_batch* b, int32_t code, const char* fmt, ...) {
@@ -2413,6 +2327,7 @@ extern "C" int32_t cosmo_hip_batch_destroy(cosmo_hip_batch* b) {
   if (b->stream) (void)hipStreamSynchronize(b->stream);
   for (void* p : b->allocs) (void)hipFree(p);
   bldl_free(b->ldl);
+  bldl_free(b->pol_plan);
   if (b->h_state) (void)hipHostFree(b->h_state);
   if (b->ev_in) (void)hipEventDestroy(b->ev_in);
   if (b->ev_out) (void)hipEventDestroy(b->ev_out);
@@ -3472,9 +3387,11 @@ extern "C" int32_t cosmo_hip_batch_optimize(cosmo_hip_batch* b, cosmo_hip_result
     if (bad >= 0) return bfail(b, COSMO_HIP_ERR_INVALID, "direct KKT solver: zero or non-finite pivot in the LDL' factorisation (member %d)", bad);
   }
   const double el = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+  b->last_status.resize((size_t)b->nprob);                  // which members cosmo_hip_batch_polish may take
   for (int k = 0; k < b->nprob; ++k) {
     cosmo_hip_result& r = results[k];
     memset(&r, 0, sizeof r);
+    b->last_status[(size_t)k] = c[k].status;
     r.status = c[k].status; r.n_rho_updates = c[k].n_rho_updates; r.iter = c[k].iter + (b->aa_on ? acc[(size_t)k].sg_iter : 0); r.safeguarding_iter = b->aa_on ? acc[(size_t)k].sg_iter : 0; r.kkt_iters_total = c[k].kkt_iters_total;
     r.kkt_solves = c[k].solves; r.cost = (double)c[k].cost; r.r_prim = (double)c[k].r_prim; r.r_dual = (double)c[k].r_dual;
     r.max_norm_prim = (double)c[k].max_norm_prim; r.max_norm_dual = (double)c[k].max_norm_dual; r.rho = (double)c[k].rho; r.iter_time = el;
@@ -4054,5 +3971,131 @@ extern "C" int32_t cosmo_hip_batch_get_scaled_problem(cosmo_hip_batch* b, int64_
 extern "C" int32_t cosmo_hip_batch_ruiz_info(cosmo_hip_batch* b, int64_t out[4]) {
   if (!b || !out || !b->ruiz_done) return bfail(b, COSMO_HIP_ERR_INVALID, "batch_ruiz_info: cosmo_hip_batch_scale_ruiz first");
   for (int i = 0; i < 4; ++i) out[i] = b->ruiz_info[i];
+  return COSMO_HIP_OK;
+}
+
+// ---- active-set polish of the Solved members (batch_polish.h; kernel: batch_polish.hip) -------------------------------------------------------
+static const char* bcone_type_name(int ty) {
+  switch (ty) {
+    case COSMO_HIP_SOC: return "SecondOrderCone";
+    case COSMO_HIP_PSD_SQUARE: return "PsdCone";
+    case COSMO_HIP_PSD_TRIANGLE: return "PsdConeTriangle";
+    case COSMO_HIP_EXP: return "ExponentialCone";
+    case COSMO_HIP_DUAL_EXP: return "DualExponentialCone";
+    case COSMO_HIP_POW: return "PowerCone";
+    case COSMO_HIP_DUAL_POW: return "DualPowerCone";
+    default: return "cone";
+  }
+}
+
+// the patterns of the batch's device matrices back on the host (set_params released its staging copies): what bldl_build reads of a HostCsr
+static int32_t bpolish_host_csr(cosmo_hip_batch* b, const BMat& M, int nrows, bool has_split, std::vector<HostCsr>& out) {
+  const size_t np = (size_t)b->nprob, nr = (size_t)nrows;
+  std::vector<long long> off(np);
+  std::vector<int> rp(np * (nr + 1)), sp;
+  BHIP(b, hipMemcpy(off.data(), M.nz_off, np * sizeof(long long), hipMemcpyDeviceToHost));
+  BHIP(b, hipMemcpy(rp.data(), M.rowptr, rp.size() * sizeof(int), hipMemcpyDeviceToHost));
+  const size_t total = (size_t)off[np - 1] + (size_t)rp[(np - 1) * (nr + 1) + nr];
+  std::vector<int> col(std::max<size_t>(total, 1));
+  if (total) BHIP(b, hipMemcpy(col.data(), M.col, total * sizeof(int), hipMemcpyDeviceToHost));
+  if (has_split) { sp.resize(std::max<size_t>(np * nr, 1)); if (np * nr) BHIP(b, hipMemcpy(sp.data(), M.split, np * nr * sizeof(int), hipMemcpyDeviceToHost)); }
+  out.assign(np, HostCsr());
+  for (size_t k = 0; k < np; ++k) {
+    HostCsr& H = out[k];
+    H.nrows = nrows;
+    H.rowptr.assign(rp.begin() + (long long)(k * (nr + 1)), rp.begin() + (long long)((k + 1) * (nr + 1)));
+    H.col.assign(col.begin() + off[k], col.begin() + off[k] + H.rowptr[nr]);
+    if (has_split) H.split.assign(sp.begin() + (long long)(k * nr), sp.begin() + (long long)((k + 1) * nr));
+  }
+  return COSMO_HIP_OK;
+}
+
+// First use: the cone check, the plan (the direct batch's, or one built here from the device patterns), the polish's own slabs and vectors.
+static int32_t bpolish_init(cosmo_hip_batch* b) {
+  if (b->pol_ready) return COSMO_HIP_OK;
+  const ConeTable& C = b->cones;
+  for (size_t c = 0; c < C.type.size(); ++c) {
+    const int ty = C.type[c];
+    if (ty != COSMO_HIP_ZERO && ty != COSMO_HIP_NONNEG && ty != COSMO_HIP_BOX)
+      return bfail(b, COSMO_HIP_ERR_UNSUPPORTED, "batch_polish: cone %d is a %s of dimension %lld; polishing takes ZeroSet, Nonnegatives and Box only", (int)c,
+                   bcone_type_name(ty), (long long)C.dim[c]);
+  }
+  const BatchDev& D = b->D;
+  const size_t np = (size_t)b->nprob, n = (size_t)b->n, m = (size_t)b->m;
+  BPolishDev& P = b->pol;
+  memset(&P, 0, sizeof P);
+  int32_t rc;
+  const bool shared = b->ldl != nullptr;
+  if (shared) P.L = D.ldl;                                  // its analysis and refill maps; Lx and y are replaced below
+  else {
+    if (b->pol_plan) { bldl_free(b->pol_plan); b->pol_plan = nullptr; }      // (an earlier call got no further than the plan)
+    {
+      std::vector<HostCsr> hPT, hA;
+      if ((rc = bpolish_host_csr(b, D.PT, (int)n, true, hPT)) || (rc = bpolish_host_csr(b, D.A, (int)m, false, hA))) return rc;
+      std::string err;
+      BLdlDev Ld;
+      rc = bldl_build(b->nprob, b->n, b->m, hPT, hA, std::vector<int64_t>(), &b->pol_plan, &Ld, err);
+      if (rc) { bldl_free(b->pol_plan); b->pol_plan = nullptr; return bfail(b, rc, "batch_polish: %s", err.c_str()); }
+      P.L = Ld;                                             // (bldl_build allocated Lx and y under its own budget rule: they are the polish's)
+    }
+  }
+  // storage budget, the rule of bldl_build: against half of the free device memory
+  const double slab = shared ? (double)np * (double)(P.L.panel + P.L.N) * sizeof(real) : 0.0;
+  const double vecs = (double)np * ((double)(3 * m + 2 * (n + m) + BPOLISH_INFO) * sizeof(real) + (double)m + 8.0);
+  size_t fr = 0, tot = 0;
+  BHIP(b, hipMemGetInfo(&fr, &tot));
+  if (slab + vecs > 0.5 * (double)fr)
+    return bfail(b, COSMO_HIP_ERR_UNSUPPORTED, "batch_polish: the polish slabs need %.1f MiB (panel_size %lld x %d problems x %d bytes, plus %.1f MiB of work vectors), over "
+                 "half of the %.1f MiB of free device memory", slab / 1048576.0, (long long)P.L.panel, b->nprob, (int)sizeof(real), vecs / 1048576.0, (double)fr / 1048576.0);
+  if (shared && ((rc = balloc(b, &P.L.Lx, np * (size_t)P.L.panel)) || (rc = balloc(b, &P.L.y, np * (size_t)P.L.N)))) return rc;
+  if ((rc = balloc(b, &P.mask, np * m)) || (rc = balloc(b, &P.shat, np * m)) || (rc = balloc(b, &P.muc, np * m)) || (rc = balloc(b, &P.sc, np * m)) ||
+      (rc = balloc(b, &P.t, np * (n + m))) || (rc = balloc(b, &P.res, np * (n + m))) || (rc = balloc(b, &P.status, np)) ||
+      (rc = balloc(b, &P.info, np * BPOLISH_INFO)) || (rc = balloc(b, &b->d_pol_elig, np))) return rc;
+  P.nprob = b->nprob; P.n = (int)n; P.m = (int)m;
+  P.A = D.A; P.PT = D.PT;
+  P.q = D.q; P.b = D.b; P.Dinv = D.Dinv; P.Einv = D.Einv; P.cinv = D.cinv;
+  P.meta = D.meta; P.box_l = D.box_l; P.box_u = D.box_u; P.nbox = D.nbox;
+  P.rho = D.rho; P.w = D.w; P.w_prev = D.w_prev; P.s = D.s; P.mu = D.mu; P.ctl = D.ctl;
+  P.elig = b->d_pol_elig;
+  int cus = 0;
+  BHIP(b, hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, b->device));
+  b->pol_grid = std::max(cus, 1);                           // one persistent workgroup per CU at most
+  b->pol_ready = true;
+  return COSMO_HIP_OK;
+}
+
+extern "C" int32_t cosmo_hip_batch_polish(cosmo_hip_batch* b, double delta, int32_t refine_iter) {
+  if (!b) return COSMO_HIP_ERR_INVALID;
+  if (!b->finalized || b->last_status.empty()) return bfail(b, COSMO_HIP_ERR_INVALID, "batch_polish: nothing to polish before cosmo_hip_batch_optimize");
+  if (!(delta > 0.0) || !std::isfinite(delta) || refine_iter < 0)
+    return bfail(b, COSMO_HIP_ERR_INVALID, "batch_polish: need delta > 0 and refine_iter >= 0 (got %g, %d)", delta, (int)refine_iter);
+  if (hipSetDevice(b->device) != hipSuccess) return bfail(b, COSMO_HIP_ERR_HIP, "hipSetDevice failed");
+  { const int32_t rc = bpolish_init(b); if (rc) return rc; }
+  BPolishDev& P = b->pol;
+  P.delta = (real)delta; P.refine_iter = (int)refine_iter; P.big = (real)b->prm.cosmo_infty_min_scaling; P.unscale = b->prm.unscale_residuals ? 1 : 0;
+  b->pol_elig.resize((size_t)b->nprob);
+  for (int k = 0; k < b->nprob; ++k) b->pol_elig[(size_t)k] = b->last_status[(size_t)k] == COSMO_HIP_SOLVED ? 1 : 0;
+  BHIP(b, hipMemcpyAsync(b->d_pol_elig, b->pol_elig.data(), sizeof(int) * (size_t)b->nprob, hipMemcpyHostToDevice, b->stream));
+  BHIP(b, bpolish_launch(b->stream, P, b->pol_grid));
+  BHIP(b, hipStreamSynchronize(b->stream));
+  b->pol_ran = true;
+  return COSMO_HIP_OK;
+}
+
+extern "C" int32_t cosmo_hip_batch_polish_info(cosmo_hip_batch* b, int32_t* status, double* out) {
+  if (!b) return COSMO_HIP_ERR_INVALID;
+  if (!b->pol_ran) return bfail(b, COSMO_HIP_ERR_INVALID, "batch_polish_info: cosmo_hip_batch_polish first");
+  if (hipSetDevice(b->device) != hipSuccess) return bfail(b, COSMO_HIP_ERR_HIP, "hipSetDevice failed");
+  const size_t np = (size_t)b->nprob;
+  if (status) BHIP(b, hipMemcpyAsync(status, b->pol.status, sizeof(int32_t) * np, hipMemcpyDefault, b->stream));     // (host or device memory)
+  std::vector<real> h(np * BPOLISH_INFO);
+  if (out) BHIP(b, hipMemcpyAsync(h.data(), b->pol.info, sizeof(real) * h.size(), hipMemcpyDeviceToHost, b->stream));
+  BHIP(b, hipStreamSynchronize(b->stream));
+  if (out) for (size_t k = 0; k < np; ++k) {
+    const real* v = h.data() + k * BPOLISH_INFO;
+    for (int j = 0; j < 4; ++j) out[4 * k + j] = (double)v[j];
+    out[4 * np + k] = (double)v[5];
+    out[5 * np + k] = (double)v[4];
+  }
   return COSMO_HIP_OK;
 }

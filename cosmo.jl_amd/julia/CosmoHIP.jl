@@ -474,6 +474,21 @@ function batch_direct_counts(::Type{T}, b::Ptr{Cvoid}, nprob::Integer) where {T 
     return out
 end
 
+# Polishing of the members the last optimize reported Solved (csrc/batch_polish.hip; ZeroSet / Nonnegatives / Box batches): the active rows guessed from the
+# iterates, one regularised LDL' solve with `refine_iter` refinement steps, accepted per member only if neither residual grew.  Returns what
+# cosmo_hip_batch_polish_info reports: status (1 accepted, -1 rejected, 0 not attempted), the residuals before, the candidate's residuals and cost, and the
+# number of active rows, one entry per member each.  Accepted members' x, s, mu are then the polished ones for every later read of the batch.
+function batch_polish!(::Type{T}, b::Ptr{Cvoid}, nprob::Integer; delta::Float64 = T == Float32 ? 1e-3 : 1e-6, refine_iter::Integer = 3) where {T <: HipFloat}
+    rc = ccall((:cosmo_hip_batch_polish, libpath(T)), Int32, (Ptr{Cvoid}, Cdouble, Int32), b, delta, Int32(refine_iter))
+    rc == 0 || error("cosmo_hip_batch_polish failed (code $rc)")
+    status = zeros(Int32, nprob); out = zeros(Float64, 6 * nprob)
+    rc = ccall((:cosmo_hip_batch_polish_info, libpath(T)), Int32, (Ptr{Cvoid}, Ptr{Int32}, Ptr{Cdouble}), b, status, out)
+    rc == 0 || error("cosmo_hip_batch_polish_info failed (code $rc)")
+    q = reshape(out[1:4 * nprob], 4, nprob)
+    return (status = status, r_prim_before = q[1, :], r_dual_before = q[2, :], r_prim = q[3, :], r_dual = q[4, :],
+            active_rows = Int.(out[4 * nprob + 1:5 * nprob]), cost = out[5 * nprob + 1:6 * nprob])
+end
+
 # Resident re-solves on a raw cosmo_hip_batch* `b` / cosmo_hip_batch_group* `g` of library T (include/cosmo_hip.h): update!(model; q, b) of members on
 # the device (raw, unscaled vectors; `nothing` leaves a vector alone), then optimize! again from the batch's own iterates.  batch_set_scaling_full!
 # goes before set_params (D, E, c themselves: the device scales with them); the others after it.  k is 0-based.

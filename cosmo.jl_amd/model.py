@@ -143,6 +143,15 @@ class Settings:
     # Where no decision of the scaling depends on the order of a sum the result is the host's to the bit; elsewhere it agrees to a few units in the last
     # place (two means are summed in another order than NumPy's, and a last-place difference of c or of a cone's E feeds the later rounds).
     batch_device_scaling: bool = False
+    # polishing of the solved members in batch mode (not a field of COSMO.Settings; what OSQP calls `polish`): after the ADMM loop every Solved member's
+    # active rows are guessed from its iterates, the equality-constrained KKT system on them is solved once by a regularised LDL' factor with
+    # polish_refine_iter steps of iterative refinement, and the result replaces x, y, s, obj_val and the residuals of the member if neither residual got
+    # worse (csrc/batch_polish.hip, cosmo_hip_batch_polish; Result.info.polish_status: 1 accepted, -1 rejected, 0 not attempted).  For optimize_batch,
+    # BatchSolver and optimize() with persistent_kernel=True, on single-structure batches of ZeroSet / Nonnegatives / Box models; anything else raises
+    # NotImplementedError.  polish_delta is the regularisation; a float32 model whose polish_delta is left at the default uses POLISH_DELTA_F32.
+    polish: bool = False
+    polish_delta: float = 1e-6
+    polish_refine_iter: int = 3
     # accepted for drop-in compatibility with COSMO.Settings (src/settings.jl:101-139); they do not touch the hot path:
     nearly_ratio: float = 100.0            # only read by the MOI wrapper (is_primal_nearly_feasible, src/MOI_wrapper.jl:558,587)
     adaptive_rho_fraction: float = 0.4     # only with adaptive_rho_interval = 0 (the automatic interval, solver.jl:244-256)
@@ -406,6 +415,9 @@ class ResultInfo:
     max_norm_dual: float
     rho_updates: List[float]
     schur: Optional[dict] = None       # SchurComplementKKTSolver on a single handle: the figures of cosmo_hip_schur_info
+    polish_status: int = 0             # Settings.polish: 1 = the polished solution was accepted, -1 = rejected, 0 = not attempted (not Solved, or polish off)
+    polish_res_prim_before: float = float("nan")       # r_prim / r_dual of the ADMM solution the polish started from (NaN: polish off)
+    polish_res_dual_before: float = float("nan")
 
 
 @dataclass
@@ -435,7 +447,8 @@ class Result:
 class DeviceBatchResult:
     """`BatchSolver.optimize(results="device")`: the unscaled solutions of all members as torch tensors on the batch's device -- x (nprob, n),
     y (nprob, m), s (nprob, m), in the batch's dtype, valid on the stream that was current at the call -- and the per-member figures the solve
-    returns to the host anyway, as host arrays of nprob entries."""
+    returns to the host anyway, as host arrays of nprob entries.  With Settings.polish, polish_status is an int32 tensor of nprob entries on the device (1 accepted,
+    -1 rejected, 0 not attempted; no host copy) and x, y, s, obj_val, r_prim, r_dual are the polished ones of the accepted members."""
     x: object
     y: object
     s: object
@@ -445,6 +458,7 @@ class DeviceBatchResult:
     r_prim: np.ndarray
     r_dual: np.ndarray
     kkt_iters_total: np.ndarray
+    polish_status: object = None
 
 
 @dataclass
@@ -919,6 +933,10 @@ def optimize(model: Model, dist=None, shard: str = "rows") -> Result:
         raise RuntimeError("The model has to be assembled! / set! before optimize!() can be called.")
     if model.settings.persistent_kernel and dist is None and model.handle is None and _fits_persistent_kernel(model):
         return _solve_shard_on_device([model], model.settings.device)[0]
+    if model.settings.polish:
+        _check_polish([model])
+        raise NotImplementedError("Settings.polish: this optimize() runs on the model's own single-problem handle, which has no polishing step; polishing "
+                                  "runs in the batch kernels (optimize_batch, BatchSolver, or persistent_kernel=True on a model that fits them)")
     t0 = time.perf_counter()
     fresh = model.handle is None
     if fresh and model.settings.decompose and getattr(model, "chordal", None) is None:
@@ -1207,6 +1225,45 @@ def prepare_batch_group(models: Sequence[Model], device: int):
     return G, st
 
 
+POLISH_DELTA_F32 = 1e-3        # regularisation of the polish factor in a float32 batch ("Polishing in batch mode": how it was chosen)
+
+
+def _check_polish(models: Sequence[Model]) -> None:
+    """Settings.polish: what cosmo_hip_batch_polish takes -- one structure, ZeroSet / Nonnegatives / Box only, no chordal decomposition, members the batch
+    kernels solve themselves.  Anything else is refused here, aloud."""
+    if not models[0].settings.polish:
+        return
+    if len({_structure_key(md) for md in models}) > 1:
+        raise NotImplementedError("Settings.polish: a mixed list runs as a batch group, which has no polishing step; polish lists of ONE structure")
+    for md in models:
+        for K in md.sets:
+            if K.kind not in (_ffi.ZERO, _ffi.NONNEG, _ffi.BOX):
+                raise NotImplementedError("Settings.polish: a model has a %s; polishing takes ZeroSet, Nonnegatives and Box constraints only" % type(K).__name__)
+        if getattr(md, "chordal", None) is not None:
+            raise NotImplementedError("Settings.polish: a chordally decomposed model cannot be polished")
+    if not _batch_kernels_take(models[0]):
+        raise NotImplementedError("Settings.polish: these settings (kkt_solver, adaptive_rho_interval = 0, accelerator variant) put every member on its own "
+                                  "single-problem handle, which has no polishing step; use a CG solver kind or QdldlKKTSolver with direct_batch=True")
+
+
+def _polish_batch(B, st: Settings, rs, status_out=None):
+    """cosmo_hip_batch_polish behind a batch's optimize() when Settings.polish is set (None otherwise): the accepted members' cost / r_prim / r_dual
+    replace those of the result records `rs`; returns Batch.polish_info()."""
+    if not st.polish:
+        return None
+    delta = float(st.polish_delta)
+    if B.dtype == np.float32 and delta == Settings.polish_delta:
+        delta = POLISH_DELTA_F32
+    B.polish(delta, int(st.polish_refine_iter))
+    info = B.polish_info()
+    if status_out is not None:
+        B.polish_info(status_out=status_out)
+    for k, r in enumerate(rs):
+        if info["status"][k] == 1:
+            r.cost = float(info["cost"][k]); r.r_prim = float(info["r_prim"][k]); r.r_dual = float(info["r_dual"][k])
+    return info
+
+
 LAST_BATCH_INFO: dict = {}     # diagnostics of the last _solve_shard_on_device call (tests / timing labs)
 
 
@@ -1217,6 +1274,7 @@ def _solve_shard_on_device(models: Sequence[Model], device: int) -> List[Result]
     if not models:
         return []
     _check_batch_psd_projection(models)
+    _check_polish(models)
     t0 = time.perf_counter()
     # one structure the persistent kernels take -> the batch directly; anything else (several structures, a PSD cone of side > batch_psd_side_max, a MINRES solver kind,
     # the automatic rho interval) -> the group, which gives every structure class its batch or, where the batch kernels refuse, one handle per problem
@@ -1225,6 +1283,7 @@ def _solve_shard_on_device(models: Sequence[Model], device: int) -> List[Result]
     t_setup = time.perf_counter() - t0
     t1 = time.perf_counter()
     rs = B.optimize()
+    pol = None if mixed else _polish_batch(B, st, rs)      # Settings.polish (a mixed list was refused above)
     LAST_BATCH_INFO.clear()
     LAST_BATCH_INFO.update(dict(problems=len(models), mixed=bool(mixed), setup_seconds=t_setup, optimize_seconds=time.perf_counter() - t1))
     if mixed:
@@ -1236,13 +1295,14 @@ def _solve_shard_on_device(models: Sequence[Model], device: int) -> List[Result]
     if not mixed and _direct_batch_of(st)[0]:
         LAST_BATCH_INFO["direct_info"] = B.direct_info()               # the LDL' form of the batch kernels ran (csrc/batch_ldl.hip)
         LAST_BATCH_INFO["direct_counts"] = B.direct_counts()
-    out = _write_back(models, B, rs, st, mixed, t0, t_setup)
+    out = _write_back(models, B, rs, st, mixed, t0, t_setup, pol)
     B.close()
     return out
 
 
-def _write_back(models, B, rs, st, mixed, t0, t_setup) -> List[Result]:
-    """The epilogue of optimize! (src/solver.jl:167-201) for every model of a batch: unscaled x, s, mu into the model, one Result each."""
+def _write_back(models, B, rs, st, mixed, t0, t_setup, pol=None) -> List[Result]:
+    """The epilogue of optimize! (src/solver.jl:167-201) for every model of a batch: unscaled x, s, mu into the model, one Result each.  pol: what
+    _polish_batch returned (the iterates and `rs` already are the polished ones of the accepted members)."""
     import time
     out = []
     for k, (md, r) in enumerate(zip(models, rs)):
@@ -1258,6 +1318,9 @@ def _write_back(models, B, rs, st, mixed, t0, t_setup) -> List[Result]:
                 md.settings.adaptive_rho_interval = chosen
         info = ResultInfo(r.r_prim, r.r_dual, r.max_norm_prim, r.max_norm_dual,
                           [r.rho_updates[i] for i in range(min(r.n_rho_updates, _ffi.MAX_RHO_UPDATES))])
+        if pol is not None:
+            info.polish_status = int(pol["status"][k])
+            info.polish_res_prim_before = float(pol["r_prim_before"][k]); info.polish_res_dual_before = float(pol["r_dual_before"][k])
         out.append(Result(x=x, y=-mu, s=s, obj_val=r.cost, iter=int(r.iter), status=_ffi.STATUS_NAMES[r.status], info=info,
                           times=ResultTimes(time.perf_counter() - t0, t_setup, r.iter_time, 0.0), kkt_iters_total=int(r.kkt_iters_total),
                           safeguarding_iter=int(r.safeguarding_iter)))
@@ -1361,6 +1424,7 @@ class BatchSolver:
         if self.mixed is None:
             _check_batch_psd_projection(models)
             self.mixed = len({_structure_key(md) for md in models}) > 1 or not _batch_kernels_take(models[0])
+        _check_polish(models)
         if self.mixed and (from_device or results == "device" or out is not None):
             raise NotImplementedError("BatchSolver.optimize: a mixed list runs as a batch group, which takes and returns no device arrays")
         if from_device or results == "device":
@@ -1391,7 +1455,10 @@ class BatchSolver:
         t_setup = time.perf_counter() - t0
         rs = self._B.optimize()
         if results == "models":
-            return _write_back(models, self._B, rs, self._st, self.mixed, t0, t_setup)
+            pol = None if self.mixed else _polish_batch(self._B, self._st, rs)
+            return _write_back(models, self._B, rs, self._st, self.mixed, t0, t_setup, pol)
+        pstat = torch.empty(nprob, dtype=torch.int32, device=dev) if self._st.polish else None
+        _polish_batch(self._B, self._st, rs, status_out=pstat)
         if out is not None:
             x, y, s = out
         else:
@@ -1402,7 +1469,7 @@ class BatchSolver:
             md.is_optimized = True
         return DeviceBatchResult(x=x, y=y, s=s, status=[_ffi.STATUS_NAMES[r.status] for r in rs], iter=np.array([r.iter for r in rs], dtype=np.int64),
                                  obj_val=np.array([r.cost for r in rs]), r_prim=np.array([r.r_prim for r in rs]), r_dual=np.array([r.r_dual for r in rs]),
-                                 kkt_iters_total=np.array([r.kkt_iters_total for r in rs], dtype=np.int64))
+                                 kkt_iters_total=np.array([r.kkt_iters_total for r in rs], dtype=np.int64), polish_status=pstat)
 
     @property
     def batch(self):

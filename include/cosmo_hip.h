@@ -615,6 +615,25 @@ COSMO_HIP_API int32_t cosmo_hip_batch_set_psd_side_max(cosmo_hip_batch* b, int32
 COSMO_HIP_API int32_t cosmo_hip_batch_direct_info(cosmo_hip_batch* b, int64_t out[8]);
 /* factorisations of every member so far (the set-up one included): out[nprob] */
 COSMO_HIP_API int32_t cosmo_hip_batch_direct_counts(cosmo_hip_batch* b, int64_t* out /* nprob */);
+/* Polishing (what OSQP calls `polish`), opt-in, for batches whose cones are all ZeroSet / Nonnegatives / Box: every member that the last
+ * cosmo_hip_batch_optimize reported Solved gets its active rows guessed from its iterates (Zero rows always; a Nonnegatives row iff s_i < y_i; a Box
+ * row at l_i iff s_i - l_i < y_i, at u_i iff u_i - s_i < -y_i, the nearer side if both; a bound beyond COSMO_INFTY * MIN_SCALING never), the
+ * equality-constrained KKT system on those rows is solved with an LDL' factor regularised by +delta / -delta and refine_iter steps of iterative
+ * refinement, and the candidate (y clipped to the sign its bound permits, s projected on the inactive rows) REPLACES the member's iterates only if it is
+ * finite and neither residual of cosmo_hip_result (r_prim, r_dual, evaluated as the loop evaluates them) is larger than that of the iterates.  Accepted:
+ * x, s, mu of the member and cost / r_prim / r_dual of its control block are the polished ones, so cosmo_hip_batch_get_iterates,
+ * cosmo_hip_batch_get_solution_device and cosmo_hip_batch_warm_restart see them; rejected or not Solved: not a bit of the member changes.  rho, the
+ * factors of a direct batch, the accelerator, iteration counters and statuses are never touched.  The polish owns its factor storage (one more slab per
+ * member, allocated by the first call) and uses the analysis of a direct batch or builds one: a CG batch can be polished too.  All members run in one
+ * launch on the batch's stream (csrc/batch_polish.hip); the call returns when it is done.  Same state, same arguments: same bits.
+ * INVALID before the first cosmo_hip_batch_optimize, for delta <= 0 or refine_iter < 0; UNSUPPORTED naming the first cone of another type, or with the
+ * sizes when the polish storage exceeds half of the free device memory. */
+COSMO_HIP_API int32_t cosmo_hip_batch_polish(cosmo_hip_batch* b, double delta, int32_t refine_iter);
+/* What the last cosmo_hip_batch_polish did.  status (nprob entries, host OR device memory; NULL: skipped): 1 accepted, -1 rejected (also: a zero or
+ * non-finite pivot), 0 not attempted (the member was not Solved).  out (host memory, 6 * nprob entries; NULL: skipped): out[4 k .. 4 k + 3] = {r_prim,
+ * r_dual of the iterates before the polish, r_prim, r_dual of the candidate} of member k, out[4 nprob + k] = its number of active rows,
+ * out[5 nprob + k] = the candidate's cost.  A member that was not attempted reports the residuals of its control block and zeros. */
+COSMO_HIP_API int32_t cosmo_hip_batch_polish_info(cosmo_hip_batch* b, int32_t* status /* nprob */, double* out /* 6 * nprob */);
 /* Resident re-solves (update!(model; q, b), src/interface.jl:187-211, then optimize! again): the batch stays on the device between solves.
  * cosmo_hip_batch_set_scaling_full: cosmo_hip_batch_set_scaling plus D, E, c themselves (before set_params); the device update scales with them, so the
  *   scaled vectors are bit-identical to the host formula q <- (D .* q) .* c, b <- E .* b.  Without it the reciprocals of Dinv, Einv, cinv are used.
