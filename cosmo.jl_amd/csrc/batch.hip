@@ -34,6 +34,7 @@
 #include "batch_devio.h"
 #include "batch_polish.h"
 #include "value_maps.h"
+#include "batch_image.h"
 
 // Per-problem state of the Anderson accelerator (k_batch_admm*<..., AA = true>; csrc/anderson.hip is the single-problem form of the same
 // algorithm).  R: the mem x mem triangular factor, column-major with leading dimension BAA_MEM.
@@ -228,7 +229,6 @@ __device__ __forceinline__ real row_pipe3(uint32_t idx, uint32_t val, const uint
 // l, l + 64, ..., the partial sums are added by the wave butterfly, the owner keeps the result; the other rows of the wave then run on row_pipe3 as
 // usual -- unless the wave holds so many long rows that walking them one after the other would cost more than its longest row.  Called by all lanes of a wave at the same point (no per-lane condition around the call: a lane without a row passes len = 0).  The sum of a
 // long row is added in lane-strided instead of left-to-right order: a batch with such rows agrees with the other kernel forms to rounding, not bit for bit.
-#define LONG_ROW 64
 // which lanes of this wave hand their row to the whole wave (wave-uniform; computed ONCE per launch and slot: the rows of a slot do not change).  One thread
 // per row costs the wave its LONGEST row (the lanes run side by side); together it costs the sum over the long rows of (entries / 64 + the butterfly,
 // ~6 trips): a wave full of equally long rows -- a dense P-like block -- keeps one thread per row (mask 0).
@@ -361,12 +361,7 @@ __device__ __forceinline__ int wave_max_int(int v) {
 }
 #endif
 
-// header of a problem's LDS image (built by build_lds_images): byte offsets from the start of the image
-// oTpr: one u32 per nonzero of A' = (position into A's values) | (row, or its position in the gathered vector) << 16 -- ONE LDS read per nonzero instead
-// of two u16 reads (round 5: the A' loop of the column pass issues 3 LDS instructions per nonzero instead of 4)
-// oAord / oTord (round 6, 0 = none): the image is stored in the SORTED order of the register-CG compute assignment -- Arp is indexed by sorted position q and
-// Aord[q] (u16) is the row stored there; Trp / Prp by the sorted position of the column, Tord[q] the column
-struct LdsHdr { int nnzA, nnzP, nbA, nbAT, nbPT, oAval, oPval, oArp, oAcol, oTrp, oTpr, oPrp, oPcol, oRbA, oRbAT, oRbPT, bytes, oAord, oTord; };
+// (struct LdsHdr, the header of a problem's LDS image: batch_image.h)
 
 template <int BS>
 struct LdsOps {
@@ -2224,24 +2219,19 @@ struct cosmo_hip_batch {
   ConeTable cones; std::vector<real> hbox_l, hbox_u; int nbox = 0;
   cosmo_hip_params prm;
   bool finalized = false, have_cones = false, have_iterates = false;
-  bool long_rows = false;                     // a row or a column of A with >= LONG_ROW entries in some problem: the LONG instantiations of the register kernel (build_lds_images)
   bool ext_cones = false;                     // the batch has cones beyond Zero / Nonnegatives / Box / SecondOrderCone (set_params): PSD of side >= 2, exponential, power
   BatchDev D;
   std::vector<void*> allocs;
   std::vector<real> hDinv, hEinv, hcinv;
   std::vector<int32_t> cls_host;
   long long iters_done = 0;
-  // LDS-resident variant (build_lds_images): one image per problem, dynamic LDS = image + gather vectors + reduction slots
-  unsigned char* d_img = nullptr; long long img_stride = 0; int lds_bytes = 0; int lds_bs = 0;
-  int reg_mode = 0;    // 0: LdsOps kernel, 1: register-resident <512,1,2>, 2: <512,2,4>
-  bool force_ext = false;
+  // LDS-resident variant (build_lds_images): one image per problem, dynamic LDS = image + gather vectors + reduction slots.  img is the host plan
+  // (batch_image.h): the form (bs, reg_mode, long_rows, force_ext), the tables that set_params uploads and the source maps of the image's value slots
+  // (um_imgA / um_imgP / um_pd: matrix-value updates; host only until the first staged update, bupd_init)
+  unsigned char* d_img = nullptr; long long img_stride = 0; int lds_bytes = 0;
+  BatchImagePlan img;
   void* d_state = nullptr; void* h_state = nullptr;     // accelerated host loop: {iter, status, need_inf} per problem (k_batch_pack_state)
   bool aa_on = false; cosmo_hip_accel_params aa_prm;      // cosmo_hip_batch_set_accelerator
-  std::vector<int> h_permA, h_permT;          // compute assignment of the register kernel (build_lds_images), uploaded by set_params
-  std::vector<int> h_posN, h_posM;            // positions of the gathered LDS vectors (build_lds_images)
-  std::vector<int> h_qposA;                   // per problem: position of row i of A in the image's (sorted) storage order
-  // sliced image of the register kernel (build_lds_images): first entry | length << 16 of every thread's rows / column; diagonal of P when P is diagonal in all problems
-  std::vector<uint32_t> h_slA, h_slT; std::vector<real> h_pdiag; std::vector<unsigned char> h_pdiag_has;
   // direct KKT solver (cosmo_hip_batch_set_direct): the switch, the requested ordering (empty: default) and the plan built by set_params
   bool direct_on = false; std::vector<int64_t> direct_perm; BLdlPlan* ldl = nullptr;
   int psd_side_max = 64;      // cosmo_hip_batch_set_psd_side_max: the largest PSD cone side set_cones accepts (64 .. 256; above 64 the block pairs run in rounds, psdwg.h)
@@ -2257,9 +2247,9 @@ struct cosmo_hip_batch {
   bool ruiz_done = false; int64_t ruiz_info[4] = {0, 0, 0, 0};
   // new matrix values on a finalised batch (cosmo_hip_batch_stage_matrices / apply_updates: k_batch_update_matrices).  Per member and destination
   // slot the index of its source in the caller's [P_nzval | A_nzval] (CSC order; entries of A carry nnzP on top): um_A for the CSR of A, um_PT for
-  // [P | A'] (set_problem, value_maps.h; A' is the caller's order itself), um_imgA / um_imgP for the member's LDS image and um_pd for its row of pdiag
-  // (build_lds_images carries them next to the values; -1: a padding slot / no entry).  Host only until the first staged update (bupd_init).
-  std::vector<std::vector<int32_t>> um_A, um_PT, um_imgA, um_imgA2, um_imgP, um_pd;
+  // [P | A'] (set_problem, value_maps.h; A' is the caller's order itself); img.um_imgA / um_imgP for the member's LDS image and img.um_pd for its row of
+  // pdiag (plan_batch_images carries them next to the values; -1: a padding slot / no entry).  Host only until the first staged update (bupd_init).
+  std::vector<std::vector<int32_t>> um_A, um_PT;
   std::vector<long long> um_nnzP, um_nnzA, um_offA, um_offPT, um_offV;     // counts; first value of member k in D.A / D.AT, in D.PT, in the staging
   const int32_t* d_umap = nullptr; const BUpdDesc* d_udesc = nullptr; unsigned char* d_mstage = nullptr;
   std::vector<int32_t> mstg_slot, mstg_mem, mstg_flag; std::vector<std::vector<real>> mstg_val;
@@ -2311,7 +2301,7 @@ extern "C" int32_t cosmo_hip_batch_create(cosmo_hip_batch** out, int32_t device_
   b->hA.resize(nprob); b->hAT.resize(nprob); b->hPT.resize(nprob);
   b->hq.assign((size_t)nprob * n, 0.0); b->hb.assign((size_t)nprob * m, 0.0);
   b->have.assign(nprob, 0); b->p_sym.assign(nprob, 0); b->caller_scaled.assign(nprob, 0);
-  b->um_A.resize(nprob); b->um_PT.resize(nprob); b->um_imgA.resize(nprob); b->um_imgA2.resize(nprob); b->um_imgP.resize(nprob); b->um_pd.resize(nprob);
+  b->um_A.resize(nprob); b->um_PT.resize(nprob);
   b->um_nnzP.assign(nprob, 0); b->um_nnzA.assign(nprob, 0);
   b->hDinv.assign((size_t)nprob * n, 1.0); b->hEinv.assign((size_t)nprob * m, 1.0); b->hcinv.assign(nprob, 1.0);
   b->hD.assign((size_t)nprob * n, 1.0); b->hE.assign((size_t)nprob * m, 1.0); b->hc.assign(nprob, 1.0);
@@ -2464,21 +2454,7 @@ extern "C" int32_t cosmo_hip_batch_set_scaling_full(cosmo_hip_batch* b, int64_t 
   return COSMO_HIP_OK;
 }
 
-static void brow_blocks(const std::vector<int>& rowptr, int nrows, std::vector<int>& rb) {
-  rb.clear(); rb.push_back(0);
-  const int ROWS_MAX = 4 * COSMO_BS;
-  int r = 0;
-  while (r < nrows) {
-    int r1 = r; long long cnt = 0;
-    while (r1 < nrows) {
-      const long long rn = (long long)rowptr[r1 + 1] - rowptr[r1];
-      if (r1 > r && (cnt + rn > COSMO_NNZ_PER_BLOCK || r1 - r >= ROWS_MAX)) break;
-      cnt += rn; ++r1;
-      if (cnt > COSMO_NNZ_PER_BLOCK) break;
-    }
-    rb.push_back(r1); r = r1;
-  }
-}
+static_assert(kRowBlockNnz == COSMO_NNZ_PER_BLOCK && kRowBlockRows == 4 * COSMO_BS, "brow_blocks (batch_image.cpp) cuts the tiles of the CSR-stream kernels");
 
 static int32_t bmat_upload(cosmo_hip_batch* b, std::vector<HostCsr>& Ms, BMat& out, int nrows, int split_col, bool has_split) {
   std::vector<int> rowptr, col, split, rb, rb_off, nb;
@@ -2509,461 +2485,105 @@ static int32_t bmat_upload(cosmo_hip_batch* b, std::vector<HostCsr>& Ms, BMat& o
   return COSMO_HIP_OK;
 }
 
-static void brow_blocks(const std::vector<int>& rowptr, int nrows, std::vector<int>& rb);
-
 // the kernel instantiation a batch runs (one place: launch_batch_admm launches it, cosmo_hip_batch_kernel_info reports its registers / scratch)
 struct BKernel { const void* fn; int bs; bool image; };
 static BKernel batch_kernel_of(const cosmo_hip_batch* b) {
   bool psd = b->ext_cones;                               // the instantiations with the cones beyond Zero / Nonnegatives / Box / SecondOrderCone
-  if (b->force_ext) psd = true;                           // COSMO_HIP_BATCH_EXT=1 (lab switch: that code is a run-time no-op without such cones)
+  if (b->img.force_ext) psd = true;                           // COSMO_HIP_BATCH_EXT=1 (lab switch: that code is a run-time no-op without such cones)
   if (b->ldl) {                                           // direct KKT solver: the streaming form only (the accelerated loop carries the PSD code, as below)
     if (b->aa_on) return {(const void*)k_batch_admm_direct<true, true>, COSMO_BS, false};
     return {psd ? (const void*)k_batch_admm_direct<true, false> : (const void*)k_batch_admm_direct<false, false>, COSMO_BS, false};
   }
   const bool img = b->d_img != nullptr;
 #if !REAL_IS_FLOAT
-  if (img && b->reg_mode == 1 && b->D.sliced) {
+  if (img && b->img.reg_mode == 1 && b->D.sliced) {
     if (b->aa_on) return {(const void*)k_batch_admm_reg<512, 1, 2, false, true, true>, 512, true};
     return {psd ? (const void*)k_batch_admm_reg<512, 1, 2, true, false, true> : (const void*)k_batch_admm_reg<512, 1, 2, false, false, true>, 512, true};
   }
 #endif
-  if (img && b->reg_mode == 1 && b->long_rows) {          // rows / columns of >= LONG_ROW entries: the cooperative passes (never with the sliced image)
+  if (img && b->img.reg_mode == 1 && b->img.long_rows) {          // rows / columns of >= LONG_ROW entries: the cooperative passes (never with the sliced image)
     if (b->aa_on) return {(const void*)k_batch_admm_reg<512, 1, 2, false, true, false, true>, 512, true};
     return {psd ? (const void*)k_batch_admm_reg<512, 1, 2, true, false, false, true> : (const void*)k_batch_admm_reg<512, 1, 2, false, false, false, true>, 512, true};
   }
-  if (img && b->reg_mode == 2 && b->long_rows) {
+  if (img && b->img.reg_mode == 2 && b->img.long_rows) {
     if (b->aa_on) return {(const void*)k_batch_admm_reg<512, 2, 4, false, true, false, true>, 512, true};
     return {psd ? (const void*)k_batch_admm_reg<512, 2, 4, true, false, false, true> : (const void*)k_batch_admm_reg<512, 2, 4, false, false, false, true>, 512, true};
   }
   if (b->aa_on) {                    // accelerated loop: register kernel (batches without PSD cones), else the LDS-image kernel (512 threads) or the streaming kernel with the PSD code (a run-time no-op without such cones)
-    if (img && b->reg_mode == 1) return {(const void*)k_batch_admm_reg<512, 1, 2, false, true>, 512, true};
-    if (img && b->reg_mode == 2) return {(const void*)k_batch_admm_reg<512, 2, 4, false, true>, 512, true};
+    if (img && b->img.reg_mode == 1) return {(const void*)k_batch_admm_reg<512, 1, 2, false, true>, 512, true};
+    if (img && b->img.reg_mode == 2) return {(const void*)k_batch_admm_reg<512, 2, 4, false, true>, 512, true};
     if (img) return {(const void*)k_batch_admm_lds<512, true, true>, 512, true};
     return {(const void*)k_batch_admm<true, true>, COSMO_BS, false};
   }
-  if (img && b->reg_mode == 1) return {psd ? (const void*)k_batch_admm_reg<512, 1, 2, true, false> : (const void*)k_batch_admm_reg<512, 1, 2, false, false>, 512, true};
-  if (img && b->reg_mode == 2) return {psd ? (const void*)k_batch_admm_reg<512, 2, 4, true, false> : (const void*)k_batch_admm_reg<512, 2, 4, false, false>, 512, true};
+  if (img && b->img.reg_mode == 1) return {psd ? (const void*)k_batch_admm_reg<512, 1, 2, true, false> : (const void*)k_batch_admm_reg<512, 1, 2, false, false>, 512, true};
+  if (img && b->img.reg_mode == 2) return {psd ? (const void*)k_batch_admm_reg<512, 2, 4, true, false> : (const void*)k_batch_admm_reg<512, 2, 4, false, false>, 512, true};
   if (img) {
     if (psd) return {(const void*)k_batch_admm_lds<512, true, false>, 512, true};      // (build_lds_images fixed 512 threads for batches with PSD / exp / pow cones)
-    if (b->lds_bs == 256) return {(const void*)k_batch_admm_lds<256, false, false>, 256, true};
-    if (b->lds_bs == 512) return {(const void*)k_batch_admm_lds<512, false, false>, 512, true};
+    if (b->img.bs == 256) return {(const void*)k_batch_admm_lds<256, false, false>, 256, true};
+    if (b->img.bs == 512) return {(const void*)k_batch_admm_lds<512, false, false>, 512, true};
     return {(const void*)k_batch_admm_lds<1024, false, false>, 1024, true};
   }
   return {psd ? (const void*)k_batch_admm<true, false> : (const void*)k_batch_admm<false, false>, COSMO_BS, false};
 }
 
-// Builds the per-problem LDS images of k_batch_admm_lds if every problem fits (u16 indices, image + work vectors within the
-// CU's LDS); otherwise leaves b->d_img = nullptr and the streaming kernel is used.  COSMO_HIP_BATCH_LDS=0 disables it,
-// COSMO_HIP_BATCH_REG=0 keeps the iterates in global memory (LdsOps kernel), COSMO_HIP_BATCH_BS selects that kernel's
-// workgroup size (256, 512 or 1024; default 512).
+// The COSMO_HIP_BATCH_* switches of the image planner, read once per set_params.  LDS=0: no image (streaming kernel); REG=0: the iterates stay in global
+// memory (LdsOps kernel); BS: that kernel's workgroup size (256, 512 or 1024; default 512); EXT=1: the extended-cone instantiations on batches without
+// such cones; SLICED / LONG / LDSCG / LDSCG_SORTED / STORE_SORTED / SORTED / COLOR = 0 disable what BatchImageOpts says of each.
+static BatchImageOpts batch_image_opts() {
+  auto off = [](const char* name) { const char* e = getenv(name); return e && atoi(e) == 0; };
+  BatchImageOpts o;
+  o.lds = !off("COSMO_HIP_BATCH_LDS"); o.reg = !off("COSMO_HIP_BATCH_REG"); o.sliced = !off("COSMO_HIP_BATCH_SLICED"); o.long_rows = !off("COSMO_HIP_BATCH_LONG");
+  o.ldscg = !off("COSMO_HIP_BATCH_LDSCG"); o.ldscg_sorted = !off("COSMO_HIP_BATCH_LDSCG_SORTED"); o.store_sorted = !off("COSMO_HIP_BATCH_STORE_SORTED");
+  o.sorted = !off("COSMO_HIP_BATCH_SORTED"); o.color = !off("COSMO_HIP_BATCH_COLOR");
+  if (const char* eb = getenv("COSMO_HIP_BATCH_BS")) o.bs = atoi(eb);
+  if (const char* ex = getenv("COSMO_HIP_BATCH_EXT")) o.ext = atoi(ex) != 0;
+  return o;
+}
+
+// The device side of the LDS images: plan_batch_images (batch_image.cpp) decides the form and builds every array on the host; here the plan meets the
+// device -- does the sliced instantiation qualify, do the PSD workspaces fit, upload, grant the dynamic LDS.  If a member does not fit (u16 indices,
+// image + work vectors within the CU's LDS) b->d_img stays nullptr and the streaming kernel is used.
 static int32_t build_lds_images(cosmo_hip_batch* b) {
-  b->d_img = nullptr; b->lds_bs = 0;
-  const char* e = getenv("COSMO_HIP_BATCH_LDS");
-  if (e && atoi(e) == 0) return COSMO_HIP_OK;
-  const long long n = b->n, m = b->m;
-  if (n > 65535 || m > 65535 || n + m == 0) return COSMO_HIP_OK;
-  int npsd = 0, nmid = 0, n3 = 0;
-  for (size_t c = 0; c < b->cones.type.size(); ++c) if (b->cones.type[c] >= COSMO_HIP_EXP && b->cones.type[c] <= COSMO_HIP_DUAL_POW) n3 += 1;
-  for (size_t c = 0; c < b->cones.type.size(); ++c)
-    if ((b->cones.type[c] == COSMO_HIP_PSD_SQUARE || b->cones.type[c] == COSMO_HIP_PSD_TRIANGLE) && b->cones.dim[c] > 1) {
-      npsd += 1;
-      if (b->cones.dim[c] > (b->cones.type[c] == COSMO_HIP_PSD_SQUARE ? 16 * 16 : 16 * 17 / 2)) nmid += 1;        // side 17 .. 64: workgroup-level Jacobi
-    }
-  int bs = 512;
-  if (const char* eb = getenv("COSMO_HIP_BATCH_BS")) { const int v = atoi(eb); if (v == 256 || v == 512 || v == 1024) bs = v; }
-  { const char* ex = getenv("COSMO_HIP_BATCH_EXT"); b->force_ext = ex && atoi(ex) != 0; }     // measure the extended-cone instantiations on batches without such cones
-  if (npsd > 0 || n3 > 0 || b->aa_on || b->force_ext) bs = 512;  // the extended-cone / accelerated instantiations of the LDS-image kernel exist for 512 threads
-  // register-resident iterates (k_batch_admm_reg, 512 threads) when the vectors fit 1-2 (n) / 2-4 (m) elements per thread
-  b->reg_mode = 0;
-  { const char* er = getenv("COSMO_HIP_BATCH_REG");
-    if (!(er && atoi(er) == 0)) {
-      if (n <= 512 && m <= 1024) b->reg_mode = 1; else if (n <= 1024 && m <= 2048) b->reg_mode = 2;
-      if (b->aa_on && (npsd > 0 || n3 > 0)) b->reg_mode = 0;   // the accelerated register kernel is instantiated without the PSD / exp / pow code (registers): the LDS-image kernel takes such batches
-      if (nmid > 0) b->reg_mode = 0;            // the block-Jacobi code on top of ~200 live registers would spill: the LDS-image kernel (187 VGPRs) takes such batches
-      if (b->reg_mode) bs = 512;
-    } }
+  b->d_img = nullptr;
+  const BatchImageOpts o = batch_image_opts();
   int max_lds = 0;
   if (hipDeviceGetAttribute(&max_lds, hipDeviceAttributeMaxSharedMemoryPerBlock, b->device) != hipSuccess) return COSMO_HIP_OK;
+  BatchImageIn in;
+  in.nprob = b->nprob; in.n = b->n; in.m = b->m; in.A = &b->hA; in.AT = &b->hAT; in.PT = &b->hPT; in.um_A = &b->um_A; in.um_PT = &b->um_PT;
+  in.aa_on = b->aa_on; in.max_lds = max_lds;
+  for (size_t c = 0; c < b->cones.type.size(); ++c) if (b->cones.type[c] >= COSMO_HIP_EXP && b->cones.type[c] <= COSMO_HIP_DUAL_POW) in.n3 += 1;
+  for (size_t c = 0; c < b->cones.type.size(); ++c)
+    if ((b->cones.type[c] == COSMO_HIP_PSD_SQUARE || b->cones.type[c] == COSMO_HIP_PSD_TRIANGLE) && b->cones.dim[c] > 1) {
+      in.npsd += 1;
+      if (b->cones.dim[c] > (b->cones.type[c] == COSMO_HIP_PSD_SQUARE ? 16 * 16 : 16 * 17 / 2)) in.nmid += 1;        // side 17 .. 64: workgroup-level Jacobi
+    }
+  BatchImagePlan& pl = b->img;
+  plan_batch_images(in, o, pl);
+  std::vector<std::vector<unsigned char>> imgs, imgs2;       // the host images live until the end of this function, whichever way it ends
+  imgs.swap(pl.imgs); imgs2.swap(pl.imgs2);
+  if (!pl.error.empty()) return bfail(b, COSMO_HIP_ERR_INVALID, "%s", pl.error.c_str());
+  if (!pl.fits) return COSMO_HIP_OK;
+  const long long n = b->n, m = b->m;
+  const int bs = pl.bs, npsd = in.npsd;
   auto up16 = [](long long x) { return (x + 15) / 16 * 16; };
-  std::vector<std::vector<unsigned char>> imgs((size_t)b->nprob);
-  long long stride = 0;
-  // sliced image (register kernel <512, 1, 2>, double precision; row_sliced): built next to the row-major one, used if every problem's fits
-  std::vector<std::vector<unsigned char>> imgs2((size_t)b->nprob);
-  long long stride2 = 0;
-  const long long SL_WS0 = (long long)sizeof(real) * (512 + 2 * 512 + 2 * (512 / 64));      // xv, tv, block-sum slots in front of the image
-  bool want_sliced = !REAL_IS_FLOAT && b->reg_mode == 1 && !(getenv("COSMO_HIP_BATCH_SLICED") && atoi(getenv("COSMO_HIP_BATCH_SLICED")) == 0);
-  bool p_all_diag = true;                                                                    // P diagonal (or empty rows) in every problem: it moves into registers
-  for (int k = 0; k < b->nprob && p_all_diag; ++k) {
-    const HostCsr& PT = b->hPT[k];
-    for (long long j = 0; j < n && p_all_diag; ++j) { const int len = PT.split[j] - PT.rowptr[j]; if (len > 1 || (len == 1 && PT.col[PT.rowptr[j]] != (int)j)) p_all_diag = false; }
-  }
-  // rows / columns of A with >= LONG_ROW entries (a dense budget row, an epigraph variable): the register kernel <512, 1, 2> hands them to a whole wave in
-  // its Krylov passes (LONG instantiations, row_long_or_pipe3); the sliced image would pad the 32 rows of such a row's slice to its length: not built then
-  b->long_rows = false;
-  if (b->reg_mode != 0 && !(getenv("COSMO_HIP_BATCH_LONG") && atoi(getenv("COSMO_HIP_BATCH_LONG")) == 0)) {
-    for (int k = 0; k < b->nprob && !b->long_rows; ++k) {
-      const HostCsr &A = b->hA[k], &AT = b->hAT[k];
-      for (long long i = 0; i < m && !b->long_rows; ++i) if (A.rowptr[i + 1] - A.rowptr[i] >= LONG_ROW) b->long_rows = true;
-      for (long long j = 0; j < n && !b->long_rows; ++j) if (AT.rowptr[j + 1] - AT.rowptr[j] >= LONG_ROW) b->long_rows = true;
-    }
-    if (b->long_rows) want_sliced = false;
-  }
-  b->h_slA.clear(); b->h_slT.clear(); b->h_pdiag.clear(); b->h_pdiag_has.clear();
-  // LDS-image kernel, register-CG form of its reduced solve (batch_admm_body, RCG: the 512-thread instantiations with the extended cones): the compute
-  // assignment sorted by length (D.permA / D.permT in that form's <2, 4>-slot layout) and, with it, the image STORED in that order (round 6)
-  const bool rcg_form = b->reg_mode == 0 && bs == 512 && n <= 2 * 512 && m <= 4 * 512 && (npsd > 0 || n3 > 0 || b->aa_on || b->force_ext) &&
-                        !(getenv("COSMO_HIP_BATCH_LDSCG") && atoi(getenv("COSMO_HIP_BATCH_LDSCG")) == 0);
-  const bool rcg_sorted = rcg_form && !(getenv("COSMO_HIP_BATCH_LDSCG_SORTED") && atoi(getenv("COSMO_HIP_BATCH_LDSCG_SORTED")) == 0);
-  const bool rcg_stored = rcg_sorted && !(getenv("COSMO_HIP_BATCH_STORE_SORTED") && atoi(getenv("COSMO_HIP_BATCH_STORE_SORTED")) == 0);
-  for (int k = 0; k < b->nprob; ++k) {
-    const HostCsr &A = b->hA[k], &AT = b->hAT[k], &PT = b->hPT[k];
-    const long long nnzA = (long long)A.val.size();
-    long long nnzP = 0;
-    for (long long j = 0; j < n; ++j) nnzP += PT.split[j] - PT.rowptr[j];
-    if (nnzA > 65535 || nnzP > 65535) return COSMO_HIP_OK;
-    std::vector<int> rA, rAT, rPT;
-    // register-CG form: rows of A by decreasing length, columns by decreasing length of [P | A'] (stable: equal lengths stay in index order)
-    std::vector<int> gordA, gordT, prA, prT, prPT;
-    if (rcg_sorted) {
-      gordA.resize((size_t)m); gordT.resize((size_t)n);
-      for (long long i = 0; i < m; ++i) gordA[(size_t)i] = (int)i;
-      for (long long j = 0; j < n; ++j) gordT[(size_t)j] = (int)j;
-      std::stable_sort(gordA.begin(), gordA.end(), [&](int x, int y) { return A.rowptr[x + 1] - A.rowptr[x] > A.rowptr[y + 1] - A.rowptr[y]; });
-      auto clen = [&](int j) { return (PT.split[j] - PT.rowptr[j]) + (AT.rowptr[j + 1] - AT.rowptr[j]); };
-      std::stable_sort(gordT.begin(), gordT.end(), [&](int x, int y) { return clen(x) > clen(y); });
-      if (b->h_permA.empty()) { b->h_permA.assign((size_t)b->nprob * 4 * 512, -1); b->h_permT.assign((size_t)b->nprob * 2 * 512, -1); }
-      for (long long q = 0; q < m; ++q) {                      // position q: slot q / 512 of thread q % 512, odd slots backwards (as in the register kernel)
-        const long long sl = q / 512, t = (sl & 1) ? 511 - q % 512 : q % 512;
-        b->h_permA[(size_t)k * 4 * 512 + (size_t)(sl * 512 + t)] = gordA[(size_t)q];
-      }
-      for (long long q = 0; q < n; ++q) b->h_permT[(size_t)k * 2 * 512 + (size_t)q] = gordT[(size_t)q];
-    }
-    if (rcg_stored) {                                         // row pointers of the stored order: the tile lists of the generic loops are cut on them
-      prA.assign((size_t)m + 1, 0); prT.assign((size_t)n + 1, 0); prPT.assign((size_t)n + 1, 0);
-      for (long long q = 0; q < m; ++q) prA[(size_t)q + 1] = prA[(size_t)q] + (A.rowptr[gordA[(size_t)q] + 1] - A.rowptr[gordA[(size_t)q]]);
-      for (long long q = 0; q < n; ++q) {
-        const int c = gordT[(size_t)q];
-        prT[(size_t)q + 1] = prT[(size_t)q] + (AT.rowptr[c + 1] - AT.rowptr[c]);
-        prPT[(size_t)q + 1] = prPT[(size_t)q] + (PT.rowptr[c + 1] - PT.rowptr[c]);
-      }
-      brow_blocks(prA, (int)m, rA); brow_blocks(prT, (int)n, rAT); brow_blocks(prPT, (int)n, rPT);
-    } else {
-    brow_blocks(A.rowptr, (int)m, rA); brow_blocks(AT.rowptr, (int)n, rAT); brow_blocks(PT.rowptr, (int)n, rPT);
-    }
-    LdsHdr h; memset(&h, 0, sizeof h);
-    h.nnzA = (int)nnzA; h.nnzP = (int)nnzP; h.nbA = (int)rA.size() - 1; h.nbAT = (int)rAT.size() - 1; h.nbPT = (int)rPT.size() - 1;
-    long long o = up16(sizeof(LdsHdr));
-    h.oAval = (int)o; o = up16(o + (long long)sizeof(real) * nnzA);
-    h.oPval = (int)o; o = up16(o + (long long)sizeof(real) * nnzP);
-    h.oRbA = (int)o; o = up16(o + 16LL * h.nbA);
-    h.oRbAT = (int)o; o = up16(o + 16LL * h.nbAT);
-    h.oRbPT = (int)o; o = up16(o + 16LL * h.nbPT);
-    h.oArp = (int)o; o = up16(o + 2 * (m + 1));
-    h.oAcol = (int)o; o = up16(o + 2 * nnzA);
-    h.oTrp = (int)o; o = up16(o + 2 * (n + 1));
-    h.oTpr = (int)o; o = up16(o + 4 * nnzA);
-    h.oPrp = (int)o; o = up16(o + 2 * (n + 1));
-    h.oPcol = (int)o; o = up16(o + 2 * nnzP);
-    if (rcg_stored) { h.oAord = (int)o; o = up16(o + 2 * m); h.oTord = (int)o; o = up16(o + 2 * n); }
-    h.bytes = (int)o;
-    if (o + (long long)sizeof(real) * (n + m) + (long long)sizeof(real) * 2 * (bs / 64) > max_lds) return COSMO_HIP_OK;
-    std::vector<unsigned char>& im = imgs[(size_t)k];
-    im.assign((size_t)o, 0);
-    memcpy(im.data(), &h, sizeof h);
-    real* Aval = reinterpret_cast<real*>(im.data() + h.oAval);
-    real* Pval = reinterpret_cast<real*>(im.data() + h.oPval);
-    unsigned short* Arp = reinterpret_cast<unsigned short*>(im.data() + h.oArp);
-    unsigned short* Acol = reinterpret_cast<unsigned short*>(im.data() + h.oAcol);
-    unsigned short* Trp = reinterpret_cast<unsigned short*>(im.data() + h.oTrp);
-    uint32_t* Tpr = reinterpret_cast<uint32_t*>(im.data() + h.oTpr);
-    unsigned short* Prp = reinterpret_cast<unsigned short*>(im.data() + h.oPrp);
-    unsigned short* Pcol = reinterpret_cast<unsigned short*>(im.data() + h.oPcol);
-    // source index of every slot of Aval / Pval (cosmo_hip_batch_stage_matrices), carried through every reordering below next to the values
-    std::vector<int32_t>& srcA = b->um_imgA[(size_t)k]; std::vector<int32_t>& srcP = b->um_imgP[(size_t)k];
-    const std::vector<int32_t>& uA = b->um_A[(size_t)k]; const std::vector<int32_t>& uPT = b->um_PT[(size_t)k];
-    srcA.assign(uA.begin(), uA.end()); srcP.assign((size_t)nnzP, -1);
-    b->um_imgA2[(size_t)k].clear(); b->um_pd[(size_t)k].clear();
-    for (long long t = 0; t < nnzA; ++t) { Aval[t] = A.val[t]; Acol[t] = (unsigned short)A.col[t]; }
-    for (long long i = 0; i <= m; ++i) Arp[i] = (unsigned short)A.rowptr[i];
-    std::vector<int> cur(A.rowptr.begin(), A.rowptr.end() - 1);
-    long long pp = 0;
-    for (long long j = 0; j < n; ++j) {
-      Trp[j] = (unsigned short)AT.rowptr[j]; Prp[j] = (unsigned short)pp;
-      for (int t = PT.rowptr[j]; t < PT.split[j]; ++t) { Pval[pp] = PT.val[t]; Pcol[pp] = (unsigned short)PT.col[t]; srcP[(size_t)pp] = uPT[(size_t)t]; ++pp; }
-      for (int t = AT.rowptr[j]; t < AT.rowptr[j + 1]; ++t) {
-        const int i = AT.col[t]; const int p = cur[i]++;
-        if (p >= A.rowptr[i + 1] || A.col[p] != (int)j || A.val[p] != AT.val[t]) return bfail(b, COSMO_HIP_ERR_INVALID, "LDS image: A / A' mismatch");
-        Tpr[t] = (uint32_t)p | ((uint32_t)i << 16);
-      }
-    }
-    Trp[n] = (unsigned short)AT.rowptr[n]; Prp[n] = (unsigned short)pp;
-    auto fill_rb = [&](int off, const std::vector<int>& r, const std::vector<int>& rowptr) {
-      int* d = reinterpret_cast<int*>(im.data() + off);
-      for (size_t t = 0; t + 1 < r.size(); ++t) { d[4 * t] = r[t]; d[4 * t + 1] = r[t + 1]; d[4 * t + 2] = rowptr[r[t]]; d[4 * t + 3] = rowptr[r[t + 1]]; }
-    };
-    if (rcg_stored) {
-      // the arrays filled above in index order move to the stored order: same values, same order inside every row -- every row sum keeps its bits
-      std::vector<real> nAval((size_t)nnzA), nPval((size_t)nnzP);
-      std::vector<unsigned short> nAcol((size_t)nnzA), nPcol((size_t)nnzP);
-      std::vector<uint32_t> nTpr((size_t)nnzA);
-      std::vector<int> newstart((size_t)m);
-      std::vector<int32_t> nsrcA((size_t)nnzA), nsrcP((size_t)nnzP);
-      long long wq = 0;
-      for (long long q = 0; q < m; ++q) {
-        const int r = gordA[(size_t)q];
-        newstart[(size_t)r] = (int)wq;
-        for (int t = A.rowptr[r]; t < A.rowptr[r + 1]; ++t) { nAval[(size_t)wq] = Aval[t]; nAcol[(size_t)wq] = Acol[t]; nsrcA[(size_t)wq] = srcA[(size_t)t]; ++wq; }
-      }
-      long long wt = 0, wp = 0;
-      for (long long q = 0; q < n; ++q) {
-        const int c = gordT[(size_t)q];
-        for (int t = Trp[c]; t < Trp[c + 1]; ++t) {
-          const uint32_t pr = Tpr[t]; const int row = (int)(pr >> 16), pold = (int)(pr & 0xffffu);
-          nTpr[(size_t)wt++] = (uint32_t)(newstart[(size_t)row] + (pold - A.rowptr[row])) | ((uint32_t)row << 16);
-        }
-        for (int t = Prp[c]; t < Prp[c + 1]; ++t) { nPval[(size_t)wp] = Pval[t]; nPcol[(size_t)wp] = Pcol[t]; nsrcP[(size_t)wp] = srcP[(size_t)t]; ++wp; }
-      }
-      srcA.swap(nsrcA); srcP.swap(nsrcP);
-      std::copy(nAval.begin(), nAval.end(), Aval); std::copy(nAcol.begin(), nAcol.end(), Acol);
-      std::copy(nTpr.begin(), nTpr.end(), Tpr); std::copy(nPval.begin(), nPval.end(), Pval); std::copy(nPcol.begin(), nPcol.end(), Pcol);
-      for (long long q = 0; q <= m; ++q) Arp[q] = (unsigned short)prA[(size_t)q];
-      long long pq = 0;
-      for (long long q = 0; q < n; ++q) { Trp[q] = (unsigned short)prT[(size_t)q]; Prp[q] = (unsigned short)pq; pq += PT.split[gordT[(size_t)q]] - PT.rowptr[gordT[(size_t)q]]; }
-      Trp[n] = (unsigned short)prT[(size_t)n]; Prp[n] = (unsigned short)pq;
-      unsigned short* Aord = reinterpret_cast<unsigned short*>(im.data() + h.oAord);
-      unsigned short* Tord = reinterpret_cast<unsigned short*>(im.data() + h.oTord);
-      for (long long q = 0; q < m; ++q) Aord[q] = (unsigned short)gordA[(size_t)q];
-      for (long long q = 0; q < n; ++q) Tord[q] = (unsigned short)gordT[(size_t)q];
-      fill_rb(h.oRbA, rA, prA); fill_rb(h.oRbAT, rAT, prT); fill_rb(h.oRbPT, rPT, prPT);
-    } else {
-    fill_rb(h.oRbA, rA, A.rowptr); fill_rb(h.oRbAT, rAT, AT.rowptr); fill_rb(h.oRbPT, rPT, PT.rowptr);
-    }
-    stride = std::max(stride, o);
-    const char* e_sorted = getenv("COSMO_HIP_BATCH_SORTED");      // =0: every thread computes the rows it owns (the form until round 3)
-    if (b->reg_mode == 1 && !(e_sorted && atoi(e_sorted) == 0)) {
-      // length-sorted compute assignment (see k_batch_admm_reg): position p of the sorted order goes to slot p / 512 of thread p % 512,
-      // i.e. a wave-step covers 64 consecutive positions
-      const int JMs = b->reg_mode == 1 ? 2 : 4, JNs = b->reg_mode == 1 ? 1 : 2;
-      if (b->h_permA.empty()) { b->h_permA.assign((size_t)b->nprob * JMs * 512, -1); b->h_permT.assign((size_t)b->nprob * JNs * 512, -1); }
-      std::vector<int> ord((size_t)m);
-      for (long long i = 0; i < m; ++i) ord[(size_t)i] = (int)i;
-      std::stable_sort(ord.begin(), ord.end(), [&](int x, int y) { return A.rowptr[x + 1] - A.rowptr[x] > A.rowptr[y + 1] - A.rowptr[y]; });
-      // rows: slots alternate direction (position q of slot s goes to thread q % 512 for even s, 511 - q % 512 for odd s), so that the wave
-      // with the longest rows of one slot has the shortest of the next: the pass ends with its slowest wave
-      for (long long q = 0; q < m; ++q) {
-        const long long sl = q / 512, t = (sl & 1) ? 511 - q % 512 : q % 512;
-        b->h_permA[(size_t)k * JMs * 512 + (size_t)(sl * 512 + t)] = ord[(size_t)q];
-      }
-      const std::vector<int> ordA = ord;
-      ord.resize((size_t)n);
-      for (long long j = 0; j < n; ++j) ord[(size_t)j] = (int)j;
-      auto clen = [&](int j) { return (PT.split[j] - PT.rowptr[j]) + (AT.rowptr[j + 1] - AT.rowptr[j]); };
-      std::stable_sort(ord.begin(), ord.end(), [&](int x, int y) { return clen(x) > clen(y); });
-      for (long long q = 0; q < n; ++q) b->h_permT[(size_t)k * JNs * 512 + (size_t)q] = ord[(size_t)q];
-      // STORAGE ORDER of the image = the sorted order (round 5): the rows of A, the columns of A' and the rows of P are laid out in the order of the
-      // compute assignment, so that the 64 rows a wave works on in one trip are NEIGHBOURS in the value / index arrays -- lane l reads at (start of
-      // its row) + t with starts about one row length apart: a constant-stride access, which the LDS serves at 4.1 (b64) / 2.2 (u16) cycles per
-      // wave-read against 7.2 for the scattered reads that CSR order gives a length-sorted assignment (bench/lds_conflict_lab.hip).  Arp / Trp / Prp
-      // are indexed by sorted POSITION from here on (the register kernel derives the positions of its rows / columns from the thread index, and
-      // reads the position of the rows it owns from D.qposA); same values, same per-row order: every row sum keeps its bits.
-      if (!(getenv("COSMO_HIP_BATCH_STORE_SORTED") && atoi(getenv("COSMO_HIP_BATCH_STORE_SORTED")) == 0)) {
-        if (b->h_qposA.empty()) b->h_qposA.assign((size_t)b->nprob * m, 0);
-        std::vector<real> nAval((size_t)nnzA); std::vector<unsigned short> nAcol((size_t)nnzA), nArp((size_t)m + 1);
-        std::vector<int> newstart((size_t)m);
-        std::vector<int32_t> nsrcA((size_t)nnzA), nsrcP((size_t)nnzP);
-        long long w = 0;
-        for (long long q = 0; q < m; ++q) {
-          const int r = ordA[(size_t)q];
-          nArp[(size_t)q] = (unsigned short)w; newstart[(size_t)r] = (int)w;
-          b->h_qposA[(size_t)k * m + (size_t)r] = (int)q;
-          for (int t = A.rowptr[r]; t < A.rowptr[r + 1]; ++t) { nAval[(size_t)w] = Aval[t]; nAcol[(size_t)w] = Acol[t]; nsrcA[(size_t)w] = srcA[(size_t)t]; ++w; }
-        }
-        nArp[(size_t)m] = (unsigned short)w;
-        std::vector<uint32_t> nTpr((size_t)nnzA); std::vector<unsigned short> nTrp((size_t)n + 1), nPrp((size_t)n + 1), nPcol((size_t)nnzP);
-        std::vector<real> nPval((size_t)nnzP);
-        long long wt = 0, wp = 0;
-        for (long long q = 0; q < n; ++q) {
-          const int c = ord[(size_t)q];
-          nTrp[(size_t)q] = (unsigned short)wt; nPrp[(size_t)q] = (unsigned short)wp;
-          for (int t = Trp[c]; t < Trp[c + 1]; ++t) {
-            const uint32_t pr = Tpr[t]; const int row = (int)(pr >> 16), pold = (int)(pr & 0xffffu);
-            nTpr[(size_t)wt++] = (uint32_t)(newstart[(size_t)row] + (pold - A.rowptr[row])) | ((uint32_t)row << 16);
-          }
-          for (int t = Prp[c]; t < Prp[c + 1]; ++t) { nPval[(size_t)wp] = Pval[t]; nPcol[(size_t)wp] = Pcol[t]; nsrcP[(size_t)wp] = srcP[(size_t)t]; ++wp; }
-        }
-        srcA.swap(nsrcA); srcP.swap(nsrcP);
-        nTrp[(size_t)n] = (unsigned short)wt; nPrp[(size_t)n] = (unsigned short)wp;
-        std::copy(nAval.begin(), nAval.end(), Aval); std::copy(nAcol.begin(), nAcol.end(), Acol); std::copy(nArp.begin(), nArp.end(), Arp);
-        std::copy(nTpr.begin(), nTpr.end(), Tpr); std::copy(nTrp.begin(), nTrp.end(), Trp); std::copy(nPrp.begin(), nPrp.end(), Prp);
-        std::copy(nPval.begin(), nPval.end(), Pval); std::copy(nPcol.begin(), nPcol.end(), Pcol);
-      }
-      // Positions of the gathered vectors.  A ds_read_b64 is served 32 lanes at a time and an 8-byte slot p lies in bank pair p mod 32:
-      // the 32 rows a half-wave works on in one step gather 32 entries, and every extra entry on a busy bank pair costs an LDS cycle
-      // (random indices: ~3.4 per group).  Greedy assignment: entries by decreasing number of appearances, each to the bank pair that
-      // adds the fewest conflicts over the groups it appears in (capacity = slots of that residue), slots handed out in order.
-      const char* e_color = getenv("COSMO_HIP_BATCH_COLOR");
-      if (!(e_color && atoi(e_color) == 0)) {
-        if (b->h_posN.empty()) { b->h_posN.assign((size_t)b->nprob * n, 0); b->h_posM.assign((size_t)b->nprob * m, 0); }
-        auto assign_positions = [&](int nent, const std::vector<std::vector<int>>& groups, int* pos) {
-          std::vector<std::vector<int>> where((size_t)nent);                 // entry -> groups it appears in
-          for (size_t g = 0; g < groups.size(); ++g) for (int e : groups[g]) where[(size_t)e].push_back((int)g);
-          std::vector<int> order((size_t)nent);
-          for (int e = 0; e < nent; ++e) order[(size_t)e] = e;
-          std::stable_sort(order.begin(), order.end(), [&](int x, int y) { return where[(size_t)x].size() > where[(size_t)y].size(); });
-          std::vector<int> cap(32, 0), used(32, 0);
-          for (int q = 0; q < nent; ++q) cap[q % 32] += 1;
-          std::vector<unsigned char> cnt(groups.size() * 32, 0);
-          for (int e : order) {
-            int best = -1; long long bestc = 0;
-            for (int bk = 0; bk < 32; ++bk) {
-              if (used[bk] >= cap[bk]) continue;
-              long long c = 0;
-              for (int g : where[(size_t)e]) c += cnt[(size_t)g * 32 + bk];
-              if (best < 0 || c < bestc || (c == bestc && used[bk] < used[best])) { best = bk; bestc = c; }
-            }
-            pos[e] = best + 32 * used[best];
-            used[best] += 1;
-            for (int g : where[(size_t)e]) cnt[(size_t)g * 32 + best] += 1;
-          }
-        };
-        // groups of the x-gathers: rows computed by a half-wave in one step of the A pass; columns of P gathered by a half-wave in the column pass
-        std::vector<std::vector<int>> gN, gM;
-        for (int sl = 0; sl < JMs; ++sl)
-          for (int hw = 0; hw < 16; ++hw) {
-            int maxlen = 0;
-            for (int t = 32 * hw; t < 32 * hw + 32; ++t) { const int r = b->h_permA[(size_t)k * JMs * 512 + (size_t)sl * 512 + t]; if (r >= 0) maxlen = std::max(maxlen, A.rowptr[r + 1] - A.rowptr[r]); }
-            for (int st = 0; st < maxlen; ++st) {
-              std::vector<int> g;
-              for (int t = 32 * hw; t < 32 * hw + 32; ++t) { const int r = b->h_permA[(size_t)k * JMs * 512 + (size_t)sl * 512 + t]; if (r >= 0 && A.rowptr[r] + st < A.rowptr[r + 1]) g.push_back(A.col[A.rowptr[r] + st]); }
-              if (g.size() > 1) gN.push_back(g);
-            }
-          }
-        for (int sl = 0; sl < JNs; ++sl)
-          for (int hw = 0; hw < 16; ++hw) {
-            int maxp = 0, maxt = 0;
-            for (int t = 32 * hw; t < 32 * hw + 32; ++t) {
-              const int c = b->h_permT[(size_t)k * JNs * 512 + (size_t)sl * 512 + t];
-              if (c >= 0) { maxp = std::max(maxp, PT.split[c] - PT.rowptr[c]); maxt = std::max(maxt, AT.rowptr[c + 1] - AT.rowptr[c]); }
-            }
-            for (int st = 0; st < maxp; ++st) {
-              std::vector<int> g;
-              for (int t = 32 * hw; t < 32 * hw + 32; ++t) { const int c = b->h_permT[(size_t)k * JNs * 512 + (size_t)sl * 512 + t]; if (c >= 0 && PT.rowptr[c] + st < PT.split[c]) g.push_back(PT.col[PT.rowptr[c] + st]); }
-              if (g.size() > 1) gN.push_back(g);
-            }
-            for (int st = 0; st < maxt; ++st) {
-              std::vector<int> g;
-              for (int t = 32 * hw; t < 32 * hw + 32; ++t) { const int c = b->h_permT[(size_t)k * JNs * 512 + (size_t)sl * 512 + t]; if (c >= 0 && AT.rowptr[c] + st < AT.rowptr[c + 1]) g.push_back(AT.col[AT.rowptr[c] + st]); }
-              if (g.size() > 1) gM.push_back(g);
-            }
-          }
-        int* pN = b->h_posN.data() + (size_t)k * n;
-        int* pM = b->h_posM.data() + (size_t)k * m;
-        assign_positions((int)n, gN, pN);
-        assign_positions((int)m, gM, pM);
-        // the image's gather indices become positions
-        std::vector<unsigned char>& im2 = imgs[(size_t)k];
-        unsigned short* Acol2 = reinterpret_cast<unsigned short*>(im2.data() + h.oAcol);
-        uint32_t* Tpr2 = reinterpret_cast<uint32_t*>(im2.data() + h.oTpr);
-        unsigned short* Pcol2 = reinterpret_cast<unsigned short*>(im2.data() + h.oPcol);
-        for (long long t = 0; t < nnzA; ++t) { Acol2[t] = (unsigned short)pN[Acol2[t]]; Tpr2[t] = (Tpr2[t] & 0xffffu) | ((uint32_t)pM[Tpr2[t] >> 16] << 16); }
-        for (long long t = 0; t < nnzP; ++t) Pcol2[t] = (unsigned short)pN[Pcol2[t]];
-      }
-      // ---- the sliced image of this problem (see row_sliced): from the final arrays above (stored in sorted order, gather indices = positions) ----
-      if (want_sliced && b->h_qposA.empty()) want_sliced = false;                 // needs the sorted storage order (Arp / Trp / Prp indexed by position)
-      if (want_sliced) {
-        if (b->h_slA.empty()) {
-          b->h_slA.assign((size_t)b->nprob * 2 * 512, 0u); b->h_slT.assign((size_t)b->nprob * 512, 0u);
-          if (p_all_diag) { b->h_pdiag.assign((size_t)b->nprob * n, R(0.0)); b->h_pdiag_has.assign((size_t)b->nprob * n, 0); }
-        }
-        auto qA = [&](int j, int t) { return 512 * j + ((j & 1) ? 511 - t : t); };        // slot j of thread t computes the row at this sorted position
-        long long offA[32], LA[32], offT[16], LT[16], curA = 0, curT = 0, needA = 0, needT = 0;
-        for (int j = 0; j < 2; ++j) for (int sx = 0; sx < 16; ++sx) {
-          long long L = 0;
-          for (int l = 0; l < 32; ++l) { const int q = qA(j, 32 * sx + l); if (q < m) L = std::max<long long>(L, Arp[q + 1] - Arp[q]); }
-          offA[j * 16 + sx] = curA; LA[j * 16 + sx] = L; curA += 32 * L;
-        }
-        for (int sx = 0; sx < 16; ++sx) {
-          long long L = 0;
-          for (int l = 0; l < 32; ++l) { const int q = 32 * sx + l; if (q < n) L = std::max<long long>(L, Trp[q + 1] - Trp[q]); }
-          offT[sx] = curT; LT[sx] = L; curT += 32 * L;
-        }
-        // a lane runs to its WAVE's longest row and reads two trips ahead: into the slices behind its own, or into the zero tail sized here
-        for (int j = 0; j < 2; ++j) for (int sx = 0; sx < 16; ++sx) needA = std::max(needA, offA[j * 16 + sx] + 32 * (std::max(LA[j * 16 + (sx & ~1)], LA[j * 16 + (sx | 1)]) + 2));
-        for (int sx = 0; sx < 16; ++sx) needT = std::max(needT, offT[sx] + 32 * (std::max(LT[sx & ~1], LT[sx | 1]) + 2));
-        const long long nS = std::max(curA, needA), nT = std::max(curT, needT);
-        LdsHdr h2; memset(&h2, 0, sizeof h2);
-        h2.nnzA = (int)nS; h2.nnzP = p_all_diag ? 0 : (int)nnzP;
-        long long o2 = up16(sizeof(LdsHdr));
-        h2.oAval = (int)o2; o2 = up16(o2 + (long long)sizeof(real) * nS);
-        h2.oTpr = (int)o2; o2 = up16(o2 + 4 * nT);
-        h2.oAcol = (int)o2; o2 = up16(o2 + 2 * nS);
-        if (!p_all_diag) {
-          h2.oPval = (int)o2; o2 = up16(o2 + (long long)sizeof(real) * nnzP);
-          h2.oPrp = (int)o2; o2 = up16(o2 + 2 * (n + 1));
-          h2.oPcol = (int)o2; o2 = up16(o2 + 2 * nnzP);
-        }
-        h2.bytes = (int)o2;
-        if (nS > 65535 || nT > 65535 || SL_WS0 + o2 > max_lds || SL_WS0 + h2.oAval + (long long)sizeof(real) * nS >= (1LL << 18)) want_sliced = false;
-        else {
-          std::vector<unsigned char>& i2 = imgs2[(size_t)k];
-          i2.assign((size_t)o2, 0);
-          memcpy(i2.data(), &h2, sizeof h2);
-          real* Aval2 = reinterpret_cast<real*>(i2.data() + h2.oAval);
-          unsigned short* Acol2s = reinterpret_cast<unsigned short*>(i2.data() + h2.oAcol);
-          uint32_t* Tpr2s = reinterpret_cast<uint32_t*>(i2.data() + h2.oTpr);
-          std::vector<long long> newpos((size_t)std::max<long long>(nnzA, 1), 0);
-          std::vector<int32_t>& srcA2 = b->um_imgA2[(size_t)k];
-          srcA2.assign((size_t)nS, -1);                                                  // (the zero padding has no source)
-          for (int j = 0; j < 2; ++j) for (int sx = 0; sx < 16; ++sx) for (int l = 0; l < 32; ++l) {
-            const int t = 32 * sx + l, q = qA(j, t);
-            const long long off = offA[j * 16 + sx] + l;
-            const long long start = q < m ? Arp[q] : 0, len = q < m ? Arp[q + 1] - Arp[q] : 0;
-            b->h_slA[((size_t)k * 2 + (size_t)j) * 512 + (size_t)t] = (uint32_t)off | ((uint32_t)len << 16);
-            for (long long tt = 0; tt < len; ++tt) {
-              const long long e = off + 32 * tt;
-              Aval2[e] = Aval[start + tt]; srcA2[(size_t)e] = srcA[(size_t)(start + tt)]; Acol2s[e] = (unsigned short)(Acol[start + tt] * (unsigned)sizeof(real)); newpos[(size_t)(start + tt)] = e;
-            }
-          }
-          for (int sx = 0; sx < 16; ++sx) for (int l = 0; l < 32; ++l) {
-            const int q = 32 * sx + l;
-            const long long off = offT[sx] + l;
-            const long long start = q < n ? Trp[q] : 0, len = q < n ? Trp[q + 1] - Trp[q] : 0;
-            b->h_slT[(size_t)k * 512 + (size_t)q] = (uint32_t)off | ((uint32_t)len << 16);
-            for (long long tt = 0; tt < len; ++tt) {
-              const uint32_t pr = Tpr[start + tt];
-              Tpr2s[off + 32 * tt] = (uint32_t)(SL_WS0 + h2.oAval + (long long)sizeof(real) * newpos[(size_t)(pr & 0xffffu)]) | ((pr >> 16) << 21);
-            }
-          }
-          if (!p_all_diag) {
-            memcpy(i2.data() + h2.oPval, Pval, (size_t)nnzP * sizeof(real));
-            memcpy(i2.data() + h2.oPrp, Prp, (size_t)(n + 1) * 2);
-            memcpy(i2.data() + h2.oPcol, Pcol, (size_t)nnzP * 2);
-          } else {
-            b->um_pd[(size_t)k].assign((size_t)n, -1);
-            for (long long j = 0; j < n; ++j) if (PT.split[j] > PT.rowptr[j]) { b->h_pdiag[(size_t)k * n + (size_t)j] = PT.val[PT.rowptr[j]]; b->h_pdiag_has[(size_t)k * n + (size_t)j] = 1; b->um_pd[(size_t)k][(size_t)j] = uPT[(size_t)PT.rowptr[j]]; }
-          }
-          stride2 = std::max(stride2, o2);
-        }
-      }
-    }
-  }
   // the sliced image replaces the row-major one if every problem's fits (with at least one wave workspace of the small PSD cones where the batch has such
   // cones) and the sliced instantiation has no static LDS in front of the dynamic block (its gathered vectors must start at LDS address 0)
-  bool use_sliced = want_sliced && !b->h_slA.empty() && b->reg_mode == 1;
+  bool use_sliced = pl.want_sliced && !pl.slA.empty() && pl.reg_mode == 1;
 #if REAL_IS_FLOAT
   use_sliced = false;
 #else
-  if (use_sliced && npsd > 0 && (max_lds - up16(SL_WS0 + stride2)) / PSD16_WS_STRIDE < 1) use_sliced = false;
+  if (use_sliced && npsd > 0 && (max_lds - up16(SL_WS0 + pl.stride2)) / PSD16_WS_STRIDE < 1) use_sliced = false;
   if (use_sliced) {
     const void* fs = b->aa_on ? (const void*)k_batch_admm_reg<512, 1, 2, false, true, true>
-                              : ((npsd > 0 || n3 > 0 || b->force_ext) ? (const void*)k_batch_admm_reg<512, 1, 2, true, false, true> : (const void*)k_batch_admm_reg<512, 1, 2, false, false, true>);
+                              : ((npsd > 0 || in.n3 > 0 || pl.force_ext) ? (const void*)k_batch_admm_reg<512, 1, 2, true, false, true> : (const void*)k_batch_admm_reg<512, 1, 2, false, false, true>);
     hipFuncAttributes fa;
     if (hipFuncGetAttributes(&fa, fs) != hipSuccess || fa.sharedSizeBytes != 0) { (void)hipGetLastError(); use_sliced = false; }
   }
 #endif
-  if (use_sliced) { imgs.swap(imgs2); stride = stride2; b->um_imgA.swap(b->um_imgA2); }
-  else { b->h_slA.clear(); b->h_slT.clear(); b->h_pdiag.clear(); b->h_pdiag_has.clear(); for (auto& v : b->um_pd) v.clear(); }
-  for (auto& v : b->um_imgA2) std::vector<int32_t>().swap(v);
+  if (use_sliced) { imgs.swap(imgs2); pl.stride = pl.stride2; pl.um_imgA.swap(pl.um_imgA2); }
+  else { pl.slA.clear(); pl.slT.clear(); pl.pdiag.clear(); pl.pdiag_has.clear(); for (auto& v : pl.um_pd) v.clear(); }
+  for (auto& v : pl.um_imgA2) std::vector<int32_t>().swap(v);
+  const long long stride = pl.stride;
   b->D.sliced = use_sliced ? 1 : 0;
   unsigned char* d = nullptr;
   BHIP(b, hipMalloc((void**)&d, (size_t)stride * b->nprob));
@@ -2976,16 +2596,14 @@ static int32_t build_lds_images(cosmo_hip_batch* b) {
   int nws = 0;
   if (npsd > 0) {
     nws = (int)std::min<long long>(bs / 64, (max_lds - ws_base) / PSD16_WS_STRIDE);
-    if (nws < (nmid > 0 ? 4 : 1)) { b->reg_mode = 0; return COSMO_HIP_OK; }       // (the image is released with the batch); side 17 .. 64 needs four (one per block pair)
+    if (nws < (in.nmid > 0 ? 4 : 1)) { pl.reg_mode = 0; return COSMO_HIP_OK; }       // (the image is released with the batch); side 17 .. 64 needs four (one per block pair)
   }
   b->D.psd_nws = nws;
-  { const char* ec = getenv("COSMO_HIP_BATCH_LDSCG");
-    b->D.regcg = (bs == 512 && n <= 2 * 512 && m <= 4 * 512 && !(ec && atoi(ec) == 0)) ? 1 : 0; }
-  if (!b->D.regcg || b->reg_mode != 0) { if (rcg_sorted) { b->h_permA.clear(); b->h_permT.clear(); } }
-  b->d_img = d; b->img_stride = stride; b->lds_bs = bs;
+  b->D.regcg = (bs == 512 && n <= 2 * 512 && m <= 4 * 512 && o.ldscg) ? 1 : 0;
+  b->d_img = d; b->img_stride = stride;
   b->lds_bytes = (int)(npsd > 0 ? ws_base + (long long)nws * PSD16_WS_STRIDE
                                 : (use_sliced ? SL_WS0 + stride : stride + (long long)sizeof(real) * (n + m) + (long long)sizeof(real) * 2 * (bs / 64)));
-  const void* fn = batch_kernel_of(b).fn;                  // (d_img, reg_mode, sliced, lds_bs are set: the instantiation launch_batch_admm will launch)
+  const void* fn = batch_kernel_of(b).fn;                  // (d_img, img.reg_mode, sliced, img.bs are set: the instantiation launch_batch_admm will launch)
   // The attribute belongs to the kernel INSTANTIATION, which is process-global, not to this batch: a batch group builds several classes that share an
   // instantiation with different lds_bytes, from several threads.  It is therefore set to the most the instantiation can be granted -- the device maximum
   // minus the instantiation's own static LDS (every lds_bytes is <= max_lds by construction) -- so that a later, smaller class cannot lower it under an
@@ -2997,7 +2615,7 @@ static int32_t build_lds_images(cosmo_hip_batch* b) {
     if (hipFuncGetAttributes(&fa, fn) == hipSuccess) grant = max_lds - (int)fa.sharedSizeBytes;
     if (grant < b->lds_bytes || hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, grant) != hipSuccess) {
       (void)hipGetLastError();
-      b->d_img = nullptr; b->reg_mode = 0;          // the device does not grant that much LDS: streaming kernel
+      b->d_img = nullptr; pl.reg_mode = 0;          // the device does not grant that much LDS: streaming kernel
     } }
   return COSMO_HIP_OK;
 }
@@ -3042,25 +2660,25 @@ extern "C" int32_t cosmo_hip_batch_set_params(cosmo_hip_batch* b, const cosmo_hi
     if ((ty == COSMO_HIP_PSD_SQUARE || ty == COSMO_HIP_PSD_TRIANGLE) && b->cones.dim[c] > 1) b->ext_cones = true;
   }
   if (direct) {                                            // union analysis + refill maps (needs the host CSR copies that bmat_upload releases); no LDS image
-    b->d_img = nullptr; b->reg_mode = 0; D.regcg = 0;
+    b->d_img = nullptr; b->img.reg_mode = 0; D.regcg = 0;
     const int32_t drc = bldl_build(nprob, n, m, b->hPT, b->hA, b->direct_perm, &b->ldl, &D.ldl, b->err);
     if (drc) { bldl_free(b->ldl); b->ldl = nullptr; return drc; }
   } else if ((rc = build_lds_images(b))) return rc;        // needs the host CSR copies that bmat_upload releases
-  if (b->d_img && (b->reg_mode == 1 || (b->reg_mode == 0 && D.regcg)) && !b->h_permA.empty()) {        // (no image: the streaming kernel runs and needs none of this)
-    if ((rc = bup(b, &D.permA, b->h_permA))) return rc;
-    if ((rc = bup(b, &D.permT, b->h_permT))) return rc;
-    if (!b->h_qposA.empty()) { if ((rc = bup(b, &D.qposA, b->h_qposA))) return rc; }
+  if (b->d_img && (b->img.reg_mode == 1 || (b->img.reg_mode == 0 && D.regcg)) && !b->img.permA.empty()) {        // (no image: the streaming kernel runs and needs none of this)
+    if ((rc = bup(b, &D.permA, b->img.permA))) return rc;
+    if ((rc = bup(b, &D.permT, b->img.permT))) return rc;
+    if (!b->img.qposA.empty()) { if ((rc = bup(b, &D.qposA, b->img.qposA))) return rc; }
     if (D.sliced) {
-      if ((rc = bup(b, &D.slA, b->h_slA))) return rc;
-      if ((rc = bup(b, &D.slT, b->h_slT))) return rc;
-      if (!b->h_pdiag.empty()) { if ((rc = bup(b, &D.pdiag, b->h_pdiag))) return rc; if ((rc = bup(b, &D.pdiag_has, b->h_pdiag_has))) return rc; }
+      if ((rc = bup(b, &D.slA, b->img.slA))) return rc;
+      if ((rc = bup(b, &D.slT, b->img.slT))) return rc;
+      if (!b->img.pdiag.empty()) { if ((rc = bup(b, &D.pdiag, b->img.pdiag))) return rc; if ((rc = bup(b, &D.pdiag_has, b->img.pdiag_has))) return rc; }
     }
-    if (!b->h_posN.empty()) {
-      if ((rc = bup(b, &D.posN, b->h_posN))) return rc;
-      if ((rc = bup(b, &D.posM, b->h_posM))) return rc;
+    if (!b->img.posN.empty()) {
+      if ((rc = bup(b, &D.posN, b->img.posN))) return rc;
+      if ((rc = bup(b, &D.posM, b->img.posM))) return rc;
     }
   }
-  if (!b->d_img) for (int k = 0; k < nprob; ++k) { std::vector<int32_t>().swap(b->um_imgA[(size_t)k]); std::vector<int32_t>().swap(b->um_imgP[(size_t)k]); b->um_pd[(size_t)k].clear(); }
+  if (!b->d_img) { b->img.um_imgA.clear(); b->img.um_imgP.clear(); b->img.um_pd.clear(); }      // (no image: its source maps go)
   b->um_offA.assign((size_t)nprob, 0); b->um_offPT.assign((size_t)nprob, 0); b->um_offV.assign((size_t)nprob + 1, 0);
   for (int k = 0; k + 1 < nprob; ++k) {                     // (the concatenation of bmat_upload)
     b->um_offA[(size_t)k + 1] = b->um_offA[(size_t)k] + (long long)b->hA[(size_t)k].val.size();
@@ -3492,9 +3110,9 @@ extern "C" int32_t cosmo_hip_batch_kernel_info(cosmo_hip_batch* b, int64_t* out)
   { hipFuncAttributes fa;
     BHIP(b, hipFuncGetAttributes(&fa, batch_kernel_of(b).fn));
     out[4] = fa.numRegs; out[5] = (int64_t)fa.localSizeBytes; out[6] = (int64_t)fa.sharedSizeBytes; }
-  out[7] = (b->D.permA ? 1 : 0) | ((b->d_img && b->reg_mode != 0 && b->long_rows && !b->D.sliced) ? 2 : 0);
-  out[0] = !b->d_img ? 0 : (b->reg_mode == 1 ? 2 : (b->reg_mode == 2 ? 3 : 1));
-  out[1] = (b->d_img && b->reg_mode == 1 && b->D.sliced) ? 1 : 0;
+  out[7] = (b->D.permA ? 1 : 0) | ((b->d_img && b->img.reg_mode != 0 && b->img.long_rows && !b->D.sliced) ? 2 : 0);
+  out[0] = !b->d_img ? 0 : (b->img.reg_mode == 1 ? 2 : (b->img.reg_mode == 2 ? 3 : 1));
+  out[1] = (b->d_img && b->img.reg_mode == 1 && b->D.sliced) ? 1 : 0;
   out[2] = b->d_img ? b->lds_bytes : 0;
   out[3] = (out[1] && b->D.pdiag) ? 1 : 0;
   return COSMO_HIP_OK;
@@ -3602,7 +3220,7 @@ static int32_t bupd_init(cosmo_hip_batch* b) {
   auto put = [&](int k, int d, const std::vector<int32_t>& v) { if (!v.empty()) { moff[(size_t)k * BUPD_ND + d] = (long long)maps.size(); maps.insert(maps.end(), v.begin(), v.end()); } };
   for (int k = 0; k < nprob; ++k) {
     put(k, 0, b->um_A[(size_t)k]); put(k, 2, b->um_PT[(size_t)k]);
-    if (b->d_img) { put(k, 3, b->um_imgA[(size_t)k]); put(k, 4, b->um_imgP[(size_t)k]); if (b->D.pdiag) put(k, 5, b->um_pd[(size_t)k]); }
+    if (b->d_img) { put(k, 3, b->img.um_imgA[(size_t)k]); put(k, 4, b->img.um_imgP[(size_t)k]); if (b->D.pdiag) put(k, 5, b->img.um_pd[(size_t)k]); }
   }
   int32_t rc;
   if ((rc = bup(b, &b->d_umap, maps))) return rc;
@@ -3624,7 +3242,7 @@ static int32_t bupd_init(cosmo_hip_batch* b) {
       unsigned char* im = b->d_img + (size_t)k * b->img_stride;
       BHIP(b, hipMemcpy(hd.data(), im, sizeof(LdsHdr), hipMemcpyDeviceToHost));
       LdsHdr h; memcpy(&h, hd.data(), sizeof h);
-      if ((long long)b->um_imgA[(size_t)k].size() != h.nnzA || (h.nnzP != 0 && (long long)b->um_imgP[(size_t)k].size() != h.nnzP))
+      if ((long long)b->img.um_imgA[(size_t)k].size() != h.nnzA || (h.nnzP != 0 && (long long)b->img.um_imgP[(size_t)k].size() != h.nnzP))
         return bfail(b, COSMO_HIP_ERR_INVALID, "batch_stage_matrices: the image of member %d and its value maps differ in size", k);
       set(3, reinterpret_cast<real*>(im + h.oAval), h.nnzA);
       set(4, reinterpret_cast<real*>(im + h.oPval), h.nnzP);

@@ -151,12 +151,7 @@ struct FoldPlan {
   int *u_ta = nullptr, *u_tb = nullptr, *u_bptr = nullptr, *u_bsrc = nullptr, *u_ad = nullptr;
 };
 
-struct HostCsr {  // host staging of a CSR matrix (0-based)
-  int nrows = 0, ncols = 0;
-  std::vector<int> rowptr, col;
-  std::vector<real> val;
-  std::vector<int> split;
-};
+#include "host_csr.h"      // struct HostCsr: host staging of a CSR matrix
 
 enum KernelClass {
   KC_Z = 0, KC_SOC, KC_PSD, KC_RHS, KC_SPMV_AT, KC_SPMV_A, KC_OP_APPLY, KC_CG_DIR, KC_CG_UPD, KC_TAIL,

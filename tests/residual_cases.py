@@ -49,7 +49,7 @@ here is cut that way; upload_csr: grid = min(tiles, COSMO_HIP_GRID_CAP); device_
   zero_prim     A = 0, b = 0, ZeroSet rows: r_prim is exactly 0 in the loop, the rule clamps to rho_min
   tiny_dual     P = 0, q = 0, A of order 1e-20: r_dual is tiny, the rule clamps to rho_max
 
-Batch shapes (csrc/batch.hip: build_lds_images, LONG_ROW = 64): see BATCH_SHAPES."""
+Batch shapes (csrc/batch_image.cpp: choose_form, LONG_ROW = 64): see BATCH_SHAPES."""
 import dataclasses
 import functools
 import math
@@ -67,7 +67,7 @@ UNIT = {"f64": 2.0 ** -53, "f32": 2.0 ** -24}
 LD = np.longdouble
 TILE, TILE_ROWS, SMALL_OPERATOR = 256, 256, 256 * 768          # csrc/api.hip: build_row_blocks
 CHUNKED_ABOVE = 2048                                           # COSMO_NNZ_PER_BLOCK (csrc/internal.h)
-LONG_ROW = 64                                                  # csrc/batch.hip
+LONG_ROW = 64                                                  # csrc/batch_image.h
 TERMS_PRIM, TERMS_DUAL = ("Ax", "s", "b"), ("Px", "q", "ATmu")
 POSITIONS = ("first", "last", "tile_end", "idx512", "long")
 RHO, RHO_MIN, RHO_MAX, RHO_EQ, ADAPT_TOL = 0.1, 1e-6, 1e6, 1e3, 5.0     # cosmo_hip_default_params (asserted by the GPU tests)

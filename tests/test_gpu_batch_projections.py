@@ -9,11 +9,11 @@ another kernel fails), against the reference of that file applied to the FETCHED
 the reference on the CPU.  The bounds are the project's own: bit equality for simple cones and exact cases, 8 eps d ||x|| (test_project_soc),
 64 d eps ||X||_F (check_projection / SURVEY 8c), the bounds of test_projection_matches_oracle for the 3-d cones.
 
-Which form takes which case (build_lds_images, csrc/batch.hip):
-  * register kernel: n <= 512 and m <= 1024 -> <512, 1, 2>, n <= 1024 and m <= 2048 -> <512, 2, 4> ("if (n <= 512 && m <= 1024) b->reg_mode = 1; else if
-    ..."), never with a PSD cone of side 17 .. 64 ("if (nmid > 0) b->reg_mode = 0"): cases with more rows or a mid cone have no register variant;
-  * LDS-image kernel: the image and the work vectors must fit the CU's LDS ("if (o + sizeof(real) * (n + m) + ... > max_lds) return"): about 24 bytes per
-    row in Float64, so every case here (m <= 4700) fits; its workgroup size is a parameter only without extended cones ("if (npsd > 0 || n3 > 0 ...) bs =
+Which form takes which case (choose_form and plan_batch_images, csrc/batch_image.cpp):
+  * register kernel: n <= 512 and m <= 1024 -> <512, 1, 2>, n <= 1024 and m <= 2048 -> <512, 2, 4> ("if (n <= 512 && m <= 1024) pl.reg_mode = 1; else if
+    ..."), never with a PSD cone of side 17 .. 64 ("if (in.nmid > 0) pl.reg_mode = 0"): cases with more rows or a mid cone have no register variant;
+  * LDS-image kernel: the image and the work vectors must fit the CU's LDS ("if (h.bytes + sizeof(real) * (n + m) + ... > in.max_lds) return"): about 24
+    bytes per row in Float64, so every case here (m <= 4700) fits; its workgroup size is a parameter only without extended cones ("if (ext) pl.bs =
     512"), and COSMO_HIP_BATCH_LDSCG changes its code only with extended cones and m <= 2048 (rcg_form, D.regcg);
   * streaming kernel: everything."""
 import contextlib
@@ -63,7 +63,7 @@ def has_extended_cones(case):
 
 
 def variants_of(case):
-    """the kernel forms that can take the case (the lines of build_lds_images quoted in the module docstring)"""
+    """the kernel forms that can take the case (the lines of csrc/batch_image.cpp quoted in the module docstring)"""
     ext = has_extended_cones(case)
     out = ["streaming"]
     if ext:

@@ -64,7 +64,7 @@ def test_the_constants_are_the_kernels():
     src = open(os.path.join(ROOT, "cosmo.jl_amd", "csrc", "internal.h")).read()
     assert int(re.search(r"#define\s+COSMO_NNZ_PER_BLOCK\s+(\d+)", src).group(1)) == R.CHUNKED_ABOVE
     assert int(re.search(r"#define\s+COSMO_BS\s+(\d+)", src).group(1)) == R.TILE_ROWS
-    batch = open(os.path.join(ROOT, "cosmo.jl_amd", "csrc", "batch.hip")).read()
+    batch = open(os.path.join(ROOT, "cosmo.jl_amd", "csrc", "batch_image.h")).read()     # (shared by the kernels of batch.hip and the image planner)
     assert int(re.search(r"#define\s+LONG_ROW\s+(\d+)", batch).group(1)) == R.LONG_ROW
     api = open(os.path.join(ROOT, "cosmo.jl_amd", "csrc", "api.hip")).read()
     assert "if (nnz_total <= 256LL * 768) tile = 256;" in api and R.SMALL_OPERATOR == 256 * 768 and R.TILE == 256
